@@ -8,8 +8,9 @@ A "step" = one pass of the hot path (the TEncSlice::compressSlice replacement) o
 independent all-intra pictures that are already resident in HBM: synthetic 3840x2160 10-bit frames,
 encoder_intra_main10 parameters, QP 32, WaveFrontSynchro=1 (BASELINE.json configs[3], the configuration
 the metric is quoted on; it fits one GPU).  By default every step is one launch over `--frames` pictures
-(768: the wavefront fill and drain are a small share of the launch); the timed region holds exactly K steps
-between two barrier + synchronize pairs.  `--lanes L` (optional, default 1) pipelines consecutive steps over L
+(192: a step of about 15.5 s, so that `--steps 20 --warmup 5` runs as requested in about 7 minutes; the launch's
+wavefront fill and drain weigh less at `--frames 768`, the 43 s step the headline figure was quoted on); the
+timed region holds exactly K steps between two barrier + synchronize pairs.  `--lanes L` (optional, default 1) pipelines consecutive steps over L
 HIP streams (hm355_run_begin / hm355_run_wait): each step has its own picture slots and its own launch and
 step k + L is issued once step k has finished, so the drain of one step overlaps the fill of the next.
 Measured: two launches do overlap, but 2 x 192 or 4 x 160 pictures in flight run below
@@ -68,6 +69,7 @@ Profile : main10
 
 
 DISTINCT_FRAMES = 16
+INTRA4K_FRAMES = 192         # pictures per step of the headline workload by default (one launch of ~15.5 s)
 
 
 def rank_frame_numbers(rank, count=DISTINCT_FRAMES):
@@ -596,6 +598,62 @@ def run_bits(args, torch):
     enc.close()
 
 
+DUMP_SEED = 20240607
+DUMP_PICTURES = 16          # pictures of the last step whose results are written
+DUMP_CTUS = 32              # CTUs per written picture whose decision arrays and reconstructed block are written
+
+
+def step_first_slot(k, lanes, frames):
+    """first picture slot of step k (counted from 0 in a run of steps) when steps are pipelined `lanes` deep: lane k % lanes owns
+    slots [lane * frames, (lane + 1) * frames)"""
+    return (k % lanes) * frames
+
+
+def dump_intra_outputs(enc, first_slot, n, out_dir):
+    """What the last timed step of intra4k handed its caller (hm355_download of every picture slot: reconstruction, per-CTU decisions,
+    picture statistics), as float32 / float64 .npy files under `out_dir`.  A fixed, seeded sample keeps it far below 64 MB: DUMP_PICTURES
+    of the step's `n` pictures, and for each of them the per-CTU costs of every CTU plus the decision arrays and the reconstructed 64x64
+    luma / 32x32 chroma block of DUMP_CTUS CTUs (samples outside the picture read -1).  Returns the bytes written."""
+    import hm355
+    rng = np.random.default_rng(DUMP_SEED)
+    pics = np.sort(rng.choice(n, min(n, DUMP_PICTURES), replace=False))
+    ctu_idx = np.stack([np.sort(rng.choice(enc.num_ctus, min(enc.num_ctus, DUMP_CTUS), replace=False)) for _ in pics])
+    wc = (enc.w + 63) // 64
+    out = {"picture": pics.astype(np.float64), "ctu_index": ctu_idx.astype(np.float64)}
+    stats, cost, bits, dist = [], [], [], []
+    fields = {f: [] for f in hm355.CTU_DTYPE.names if f not in ("total_cost", "total_bits", "total_dist")}
+    blocks = [[], [], []]
+    for p, sel in zip(pics, ctu_idx):
+        rec, ctus, st = enc.download(first_slot + int(p))
+        stats.append(st)
+        cost.append(ctus["total_cost"]); bits.append(ctus["total_bits"]); dist.append(ctus["total_dist"])
+        for f in fields:
+            fields[f].append(ctus[f][sel])
+        for k, plane in enumerate(rec):
+            b = 64 >> (1 if k else 0)
+            for c in sel:
+                y0, x0 = (int(c) // wc) * b, (int(c) % wc) * b
+                blk = np.full((b, b), -1.0, np.float32)
+                src = plane[y0:y0 + b, x0:x0 + b]
+                blk[:src.shape[0], :src.shape[1]] = src
+                blocks[k].append(blk)
+    out["picture_stats"] = np.array(stats, np.float64)            # total bits, RD cost, distortion of each written picture
+    out["ctu_total_cost"] = np.array(cost, np.float64)
+    out["ctu_total_bits"] = np.array(bits, np.float64)
+    out["ctu_total_dist"] = np.array(dist, np.float64)
+    for f, v in fields.items():
+        out["ctu_" + f] = np.array(v, np.float32)
+    shape = (len(pics), ctu_idx.shape[1])
+    for k, name in enumerate(("rec_y", "rec_cb", "rec_cr")):
+        out[name] = np.array(blocks[k], np.float32).reshape(shape + blocks[k][0].shape)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f"output dump of {total} bytes is over 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def intra_line(args, world, rows_mode, group, steps, warmup, dt, kernel_ms, launches, total_ctus, ctus_per_rank, build_id="unknown"):
     """the JSON line of the intra4k workload (rank 0), without the CPU baseline"""
     # HBM bytes per launch from the PMC passes committed under profiles/ -- quoted only when they were taken on this very build of
@@ -626,7 +684,8 @@ def intra_line(args, world, rows_mode, group, steps, warmup, dt, kernel_ms, laun
                    "frames_per_gpu": args.frames, "ctus_per_step": total_ctus // steps, "lanes": 1 if rows_mode else args.lanes, "build_id": build_id,
                    "parallelism": (f"CTU rows of every picture sharded over {world} GPUs in bands, boundary rows handed down over RCCL send / recv, {group} pictures per pipeline stage"
                                    if rows_mode else f"pictures sharded over {world} GPU(s), 2-CTU-lag wavefront inside a picture"),
-                   "step_budget": f"warm-up + timed steps bounded to {args.budget_s:.0f} s of wall time: {warmup}+{steps} of the requested {args.warmup}+{args.steps} steps run"},
+                   "step_budget": (f"warm-up + timed steps bounded to {args.budget_s:.0f} s of wall time: {warmup}+{steps} of the requested {args.warmup}+{args.steps} steps run"
+                                   if args.budget_s > 0 else f"no wall-time bound: {warmup}+{steps} warm-up + timed steps run as requested")},
         "roofline": {"bound": "hbm", "kernel": "hm355_ctu_kernel", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
                      "avg_launch_ms": kernel_ms / max(1, launches), "launches": launches, "launches_in_flight": in_flight,
@@ -646,15 +705,23 @@ def main():
                     help="N > 1: 'pictures' = every rank its own pictures (weak scaling, no data-path transfer; default); 'rows' = every rank a band of CTU rows "
                          "of the SAME pictures, boundary rows handed down over RCCL send / recv (hm-16.2_amd/bands.py; strong scaling)")
     ap.add_argument("--group", type=int, default=0, help="--shard rows: pictures per pipeline stage (default: frames / (4 * ranks))")
-    ap.add_argument("--budget-s", type=float, default=280.0, help="wall-time bound of warm-up + timed steps (intra4k); fewer steps run when the request does not fit")
-    ap.add_argument("--frames", type=int, default=768, help="independent pictures per GPU per step")
+    ap.add_argument("--budget-s", type=float, default=0.0, help="intra4k: wall-time bound of warm-up + timed steps; fewer steps run when the request does not fit "
+                                                                "(default 0: no bound, --warmup and --steps run as requested)")
+    ap.add_argument("--frames", type=int, default=None, help="independent pictures per GPU per step (default: 192 for intra4k, 768 for the others)")
     ap.add_argument("--lanes", type=int, default=1, help="steps in flight at a time (hm355_run_begin / hm355_run_wait; 1..4)")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--qp", type=int, default=32)
     ap.add_argument("--wpp", type=int, default=0, help="--workload c3: WaveFrontSynchro (the cfg has 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="intra4k: after the timed steps, write a fixed sample of what the last step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.frames is None:
+        args.frames = INTRA4K_FRAMES if args.workload == "intra4k" else 768
+    if args.dump_outputs and (args.workload != "intra4k" or (args.shard == "rows" and args.gpus > 1)):
+        raise SystemExit("--dump-outputs covers the intra4k workload with pictures sharded per GPU")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -735,24 +802,30 @@ def main():
                 lane = k % lanes
                 if busy[lane]:
                     ms_sum += enc.run_wait(lane)
-                enc.run_begin(lane, lane * args.frames, args.frames, args.qp)
+                enc.run_begin(lane, step_first_slot(k, lanes, args.frames), args.frames, args.qp)
                 busy[lane] = True
             for lane in range(lanes):          # oldest launch first
                 l2 = (count + lane) % lanes
                 if busy[l2]:
                     ms_sum += enc.run_wait(l2)
             return ms_sum, count
-    # Warm-up.  Its first `lanes` steps are timed: when the requested warm-up + timed steps would not fit the wall budget (the driver's
-    # 600 s limit covers start-up, the steps and the CPU baseline), the warm-up stops there and as many timed steps run as fit (at least
-    # one pipeline depth); the line reports the steps actually run next to the ones requested.
-    first = min(max(1, args.warmup), lanes)
-    t0 = time.perf_counter()
-    run_steps(first)
-    barrier()
-    step_s = agree((time.perf_counter() - t0) / first, dist.ReduceOp.MAX if dist else None)
-    warmup, steps = plan_steps(step_s, args.warmup, args.steps, args.budget_s, first)
-    if warmup > first:
-        run_steps(warmup - first)
+    # Warm-up.  Without a wall budget (--budget-s 0, the default) the requested warm-up and timed steps run as they are.  With one, the
+    # warm-up's first `lanes` steps are timed: when the requested warm-up + timed steps would not fit the budget, the warm-up stops
+    # there and as many timed steps run as fit (at least one pipeline depth); the line reports the steps actually run next to the
+    # ones requested.
+    if args.budget_s > 0:
+        first = min(max(1, args.warmup), lanes)
+        t0 = time.perf_counter()
+        run_steps(first)
+        barrier()
+        step_s = agree((time.perf_counter() - t0) / first, dist.ReduceOp.MAX if dist else None)
+        warmup, steps = plan_steps(step_s, args.warmup, args.steps, args.budget_s, first)
+        if warmup > first:
+            run_steps(warmup - first)
+    else:
+        warmup, steps = args.warmup, args.steps
+        if warmup > 0:
+            run_steps(warmup)
     barrier()
     t0 = time.perf_counter()
     kernel_ms, launches = run_steps(steps)
@@ -767,6 +840,8 @@ def main():
     else:
         ctus_per_rank = enc.num_ctus * args.frames * steps
         total_ctus = ctus_per_rank * world
+    if args.dump_outputs and rank == 0:
+        dump_intra_outputs(enc, step_first_slot(steps - 1, lanes, args.frames), args.frames, args.dump_outputs)      # the last timed step
     if rank == 0:
         line = intra_line(args, world, rows_mode, group if rows_mode else 0, steps, warmup, dt, kernel_ms, launches, total_ctus, ctus_per_rank, build_id)
         if not args.no_cpu_baseline and world >= 1:

@@ -98,3 +98,55 @@ def test_bench_line_is_complete(world, rows):
     assert abs(r["achieved"] - 54278 * 2040 * 384 * 7 / (250.0 if not rows else 248.0) / 1e9) < 1e-9
     assert r["traffic"] is None and "traffic_note" in r          # no PMC record of build 0123456789ab under profiles/
     assert bench.plan_steps(9.0, 5, 20, 280.0, first=4) == (5, 20) and bench.plan_steps(30.0, 5, 20, 280.0, first=4) == (4, 5)
+
+
+def test_bench_output_dump(tmp_path):
+    """bench.py --dump-outputs on the headline workload: a fixed sample of what hm355_download hands back (here from a stand-in encoder
+    with the product's record layout), float32 / float64 only, under 64 MB, the same files from run to run"""
+    import numpy as np
+    import bench
+    import hm355
+
+    class Enc:
+        w, h = 3840, 2160
+        num_ctus = 60 * 34
+        slots = []
+
+        def download(self, slot):
+            Enc.slots.append(slot)
+            rng = np.random.default_rng(slot)
+            rec = [rng.integers(0, 1024, (self.h >> (k > 0), self.w >> (k > 0)), dtype=np.uint16) for k in range(3)]
+            ctus = np.zeros(self.num_ctus, hm355.CTU_DTYPE)
+            for f in hm355.CTU_DTYPE.names:
+                ctus[f] = rng.integers(0, 100, ctus[f].shape)
+            return rec, ctus, (float(slot), 2.0 * slot, 3.0 * slot)
+
+    # main() passes the first slot of the last timed step: the lane of step steps - 1, as run_steps launched it
+    assert [bench.step_first_slot(k, 1, 768) for k in range(3)] == [0, 0, 0]
+    assert [bench.step_first_slot(k, 3, 192) for k in range(7)] == [0, 192, 384, 0, 192, 384, 0]
+    assert [bench.step_first_slot(k, 4, 160) for k in (4, 5, 6, 7)] == [0, 160, 320, 480]
+    total = bench.dump_intra_outputs(Enc(), 768, 768, str(tmp_path / "a"))
+    assert len(Enc.slots) == bench.DUMP_PICTURES and all(768 <= k < 2 * 768 for k in Enc.slots)      # only the step's own pictures
+    bench.dump_intra_outputs(Enc(), 768, 768, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "rec_y.npy" in names and "ctu_coeff_y.npy" in names
+    assert 0 < total <= sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    pics, sel, rec_y = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("picture", "ctu_index", "rec_y"))
+    assert np.array_equal(np.load(tmp_path / "a" / "picture_stats.npy")[:, 0], 768 + pics)
+    for i in (0, len(pics) - 1):
+        rec, ctus, _ = Enc().download(768 + int(pics[i]))
+        assert np.array_equal(np.load(tmp_path / "a" / "ctu_total_cost.npy")[i], ctus["total_cost"])
+        for f in ("depth", "cbf", "coeff_y", "coeff_cr"):          # decision arrays of the sampled CTUs, in their order
+            assert np.array_equal(np.load(tmp_path / "a" / f"ctu_{f}.npy")[i], ctus[f][sel[i].astype(int)]), f
+        for j in (0, sel.shape[1] - 1):
+            c = int(sel[i, j])
+            for k, name in enumerate(("rec_y", "rec_cb", "rec_cr")):
+                b = 32 if k else 64
+                want = rec[k][(c // 60) * b:(c // 60 + 1) * b, (c % 60) * b:(c % 60 + 1) * b]
+                got = np.load(tmp_path / "a" / f"{name}.npy")[i, j]
+                assert np.array_equal(got[:want.shape[0], :want.shape[1]], want) and (got[want.shape[0]:] == -1).all(), (name, i, j)
+    bottom = [(i, j) for i in range(len(pics)) for j in range(sel.shape[1]) if sel[i, j] >= 33 * 60]      # last CTU row: 48 of 64 lines
+    assert all((rec_y[i, j, 48:] == -1).all() for i, j in bottom)
