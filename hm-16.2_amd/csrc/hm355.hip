@@ -10,6 +10,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <string>
 #include <vector>
 #include "hm355_core.h"
@@ -182,60 +183,104 @@ extern "C" __global__ void __launch_bounds__(64) hm355_transform_kernel(int inve
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
+// Device memory owned by one object: n elements of T, freed in the destructor; moved, never copied.
+template <class T> struct DevBuf {
+  T *p = nullptr; size_t n = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { reset(); }
+  operator T *() const { return p; }
+  void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+  hipError_t alloc(size_t count)                       // a new allocation (what was held is freed first)
+  {
+    reset();
+    const hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+    if (e == hipSuccess) n = count; else p = nullptr;
+    return e;
+  }
+  hipError_t ensure(size_t count, bool zero = false)   // allocated on first use (zero: and filled with zeros then, synchronously), kept afterwards
+  {
+    if (p) return hipSuccess;
+    const hipError_t e = alloc(count);
+    return e == hipSuccess && zero ? hipMemset(p, 0, count * sizeof(T)) : e;
+  }
+  hipError_t grow(size_t count) { return count > n ? alloc(count) : hipSuccess; }   // at least count elements; the contents are not kept
+};
+// Pinned host memory owned by one object (hm355_download's staging), freed in the destructor.
+struct PinnedBuf {
+  unsigned char *p = nullptr; size_t n = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete; PinnedBuf &operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { reset(); }
+  void reset() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
+  hipError_t grow(size_t bytes)                        // at least `bytes`; the contents are not kept
+  {
+    if (bytes <= n) return hipSuccess;
+    reset();
+    const hipError_t e = hipHostMalloc((void **)&p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) n = bytes; else p = nullptr;
+    return e;
+  }
+};
+static size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // sub-buffers of one allocation or blob start on 256-byte boundaries
+
+// The device buffers of a reference picture, in the order of its blob (hm355_ref_export): the three border-extended planes, then the motion
+// field after TComPic::compressMotion.  ref_buf_bytes gives their sizes.
+enum RefBuf { REF_Y, REF_CB, REF_CR, REF_PRED_MODE, REF_MV0, REF_REF_IDX0, REF_MV1, REF_REF_IDX1, REF_NBUF };
 struct hm355_ref {       // a finished picture as later pictures reference it (device buffers owned by this object)
-  RefPicDev dev;
-  std::vector<void *> owned;
+  RefPicDev dev = {};
+  DevBuf<uint8_t> buf[REF_NBUF];
 };
 struct Slot {           // one picture resident in HBM
-  FrameBuf fb;          // device pointers + slice parameters (host copy)
-  InterMeta *imeta;     // motion arrays of the slot (allocated on first inter use; kept for the deblocking pass)
-  Pel *saoSrc[3]; SaoStat *saoStat; SaoCand *saoCand; SaoBlk *saoCoded, *saoRecon;   // SAO working buffers (allocated on first use)
-  uint8_t *rawIn, *rawOut;   // file frames as they are on disk (ingest / output, allocated on first use)
-  uint8_t *bitsRaw, *bitsPacked; uint32_t *bitsSizes; CabacW *bitsSync; uint32_t *bitsFlag; InterPic *bitsIp;   // bitstream pass (allocated on first use)
+  FrameBuf fb = {};     // device pointers + slice parameters (host copy)
+  DevBuf<InterMeta> imeta;   // motion arrays of the slot (allocated on first inter use; kept for the deblocking pass)
+  DevBuf<Pel> saoSrc[3]; DevBuf<SaoStat> saoStat; DevBuf<SaoCand> saoCand; DevBuf<SaoBlk> saoCoded, saoRecon;   // SAO working buffers (allocated on first use)
+  DevBuf<uint8_t> rawIn, rawOut;   // file frames as they are on disk (ingest / output, allocated on first use)
+  DevBuf<uint8_t> bitsRaw, bitsPacked; DevBuf<uint32_t> bitsSizes; DevBuf<CabacW> bitsSync; DevBuf<uint32_t> bitsFlag; DevBuf<InterPic> bitsIp;   // bitstream pass (allocated on first use)
   // cu_qp_delta (hm355_set_dqp): device state of the picture, allocated on first use; dqpOn: the next searches of the slot run with it
-  DqpPic *dDqp; int8_t *dCtuQp; CtuDqp *dDqpOut; uint8_t *dRowFlag; int dqpOn, dqpFlagIn;
-  std::vector<int8_t> ctuQp; std::vector<uint8_t> rowFlag; hm355_slice_desc lastSlice;
+  DevBuf<DqpPic> dDqp; DevBuf<int8_t> dCtuQp; DevBuf<CtuDqp> dDqpOut; DevBuf<uint8_t> dRowFlag; int dqpOn = 0, dqpFlagIn = 0;
+  std::vector<int8_t> ctuQp; std::vector<uint8_t> rowFlag; hm355_slice_desc lastSlice = {};
 };
 #define HM_BITS_CAP_PER_CTU 16384u   /* bytes reserved per CTU in the raw substream buffers: above the raw size of a 10-bit 4:2:0 CTU (7.7 KB) */
 #define HM_MAX_LANES 4
-struct Lane {           // one launch of the search in flight: its own stream, scratch areas, work list and scheduler words
-  hipStream_t stream; hipEvent_t ev0, ev1;
-  Params *dP;           // device copy of the kernel parameters with this lane's scratch areas
-  WorkSpace *dWs; size_t wsCount;
-  WorkItem *dItems; size_t itemsCap;
-  unsigned int *dSched; // [0] ticket, [1] abort, [2] CTUs published by the launch (the spin timeout watches it)
+struct Lane {           // one launch of the search in flight: its own stream, scratch areas, work list and scheduler words (lane_init)
+  hipStream_t stream = NULL; hipEvent_t ev0 = NULL, ev1 = NULL;
+  DevBuf<Params> dP;    // device copy of the kernel parameters with this lane's scratch areas
+  DevBuf<WorkSpace> dWs;   // one scratch area per search the lane's grid can hold
+  DevBuf<WorkItem> dItems; // the work list, grown to the longest one so far
+  DevBuf<unsigned int> dSched; // [0] ticket, [1] abort, [2] CTUs published by the launch (the spin timeout watches it); lane 0: [8] ticket, [9] abort of the bitstream launch
   std::vector<WorkItem> items; std::vector<int> stepStart; std::vector<FrameBuf> fbs;
-  long long key[5]; int keyValid, fewWaves;
-  int busy, grid, inFixup;
-  Pel *dTeamWin; size_t teamCap;   // team launches (hm355_team.h): the helpers' reconstruction windows, for teamCap teams
+  long long key[5] = {}; int keyValid = 0, fewWaves = -1;   // fewWaves: the value dP holds (-1: dP not written yet)
+  int busy = 0, grid = 0, inFixup = 0;
+  DevBuf<Pel> dTeamWin; size_t teamCap = 0;   // team launches (hm355_team.h): the helpers' reconstruction windows, for teamCap teams
+  ~Lane() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (stream) (void)hipStreamDestroy(stream); }
 };
 struct hm355_ctx {
-  hm355_seq_cfg cfg;
-  Params hp;            // host copy of the kernel parameters
-  Params *dP;
-  Tables *dTab;
-  FrameBuf *dFrames;
-  WorkSpace *dWs; size_t wsCount;
-  uint8_t *arena;       // the pictures' planes, decision arrays, coefficients, statistics, CABAC states, done words: one allocation
-  int teamLdsSet;
-  unsigned char *hStage; size_t hStageBytes;   // pinned host staging of hm355_download (one picture's results), allocated on first use
-  unsigned int *dSched; unsigned int epoch;   // dSched: [0] ticket, [1] abort, [2] published CTUs of the search launch; [8] ticket, [9] abort of the bitstream launch
+  hm355_seq_cfg cfg = {};
+  Params hp;            // host copy of the kernel parameters: what lane[0].dP holds
+  DevBuf<Tables> dTab;
+  DevBuf<FrameBuf> dFrames;
+  DevBuf<uint8_t> arena;   // the pictures' planes, decision arrays, coefficients, statistics, CABAC states, done words: one allocation
+  DevBuf<unsigned long long> prof;   // diagnostic builds only (HM355_PROFILE, HM355_TRACE): Params::prof
+  int teamLdsSet = 0;
+  PinnedBuf hStage;     // pinned host staging of hm355_download (one picture's results), allocated on first use
+  unsigned int epoch = 0;
   std::vector<Slot> slots;
-  Lane lane[HM_MAX_LANES];   // lane 0 is the context's own stream / scratch (every blocking entry point); 1.. are created on first use
-  hipStream_t stream; hipEvent_t ev0, ev1;
-  double lastKernelMs; int lastLaunches; int laneShare;
+  Lane lane[HM_MAX_LANES];   // lane 0 is built with the context and serves every blocking entry point; 1.. are built on first use
+  double lastKernelMs = 0; int lastLaunches = 0, laneShare = 1;
   std::string err;
-  int numCtus;
-  void *staging; size_t stagingBytes;
-  DbkParams *dDbk;      // [max_batch] deblocking parameters of the pictures in the slots
-  SaoParams *dSao;      // [max_batch] SAO parameters / results of the pictures in the slots
-  BitsParams *dBits;    // [max_batch] bitstream pass parameters / results
-  IngestParams *dIngest; // [max_batch] ingest / output parameters
+  int numCtus = 0;
+  DevBuf<DbkParams> dDbk;      // [max_batch] deblocking parameters of the pictures in the slots
+  DevBuf<SaoParams> dSao;      // [max_batch] SAO parameters / results of the pictures in the slots
+  DevBuf<BitsParams> dBits;    // [max_batch] bitstream pass parameters / results
+  DevBuf<IngestParams> dIngest; // [max_batch] ingest / output parameters
 };
 
 #define HM_CHECK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HM355_ERR_DEVICE; } } while (0)
 
 static int fail(hm355_ctx *c, int code, const char *msg) { if (c) c->err = msg; return code; }
+static void next_epoch(hm355_ctx *c) { c->epoch++; if (c->epoch == 0) c->epoch = 1; }   // 0 is what a fresh flag array holds
 
 #ifndef HM355_BUILD_ID
 #define HM355_BUILD_ID "unknown"
@@ -251,6 +296,23 @@ static int maxItemsPerStep(int wCtu, int hCtu, int wpp, int frames)
   return best * frames;
 }
 
+// Lane l of the context: its stream, events, scratch areas, scheduler words and parameter block.  hm355_create builds lane 0 (a blocking stream:
+// the entry points that are not searches run on it too; its dP is the context's Params, which every other kernel reads); further lanes are
+// built on first use with a non-blocking stream.  dWs is not initialised.
+static int lane_init(hm355_ctx *c, int l)
+{
+  Lane &L = c->lane[l];
+  if (L.stream) return HM355_OK;
+  HM_CHECK(c, l == 0 ? hipStreamCreate(&L.stream) : hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+  HM_CHECK(c, hipEventCreate(&L.ev0)); HM_CHECK(c, hipEventCreate(&L.ev1));
+  // one scratch area per resident workgroup of the persistent grid: 256 CUs x 8 single-wave workgroups, or fewer when the batch is small
+  size_t wsCount = (size_t)c->numCtus * (size_t)c->cfg.max_batch * HM_TEAM; if (wsCount > 3072) wsCount = 3072;   // 12 searches per CU x 256 CUs is the most that can be resident; a small batch runs as teams of HM_TEAM wavefronts per CTU
+  HM_CHECK(c, L.dWs.alloc(wsCount));
+  HM_CHECK(c, L.dSched.ensure(16, true));         // 64 bytes, zeroed by a synchronous hipMemset
+  HM_CHECK(c, L.dP.alloc(1));
+  return HM355_OK;
+}
+
 extern "C" int hm355_create(const hm355_seq_cfg *cfg, hm355_ctx **out)
 {
   if (!cfg || !out) return HM355_ERR_ARG;
@@ -262,47 +324,35 @@ extern "C" int hm355_create(const hm355_seq_cfg *cfg, hm355_ctx **out)
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return HM355_ERR_NO_DEVICE;
   hm355_ctx *c = new hm355_ctx();
-  c->cfg = *cfg; c->laneShare = 1; c->lastKernelMs = 0; c->lastLaunches = 0; c->staging = NULL; c->stagingBytes = 0; c->dDbk = NULL; c->dSao = NULL; c->dBits = NULL; c->dIngest = NULL;
-  c->arena = NULL; c->dP = NULL; c->dTab = NULL; c->dFrames = NULL; c->dWs = NULL; c->wsCount = 0; c->dSched = NULL; c->epoch = 0; c->teamLdsSet = 0; c->hStage = NULL; c->hStageBytes = 0;
-  for (int l = 0; l < HM_MAX_LANES; l++) { Lane &L = c->lane[l]; L.stream = NULL; L.ev0 = L.ev1 = NULL; L.dP = NULL; L.dWs = NULL; L.wsCount = 0; L.dItems = NULL; L.itemsCap = 0; L.dSched = NULL; L.keyValid = 0; L.fewWaves = -1; L.busy = 0; L.grid = 0; L.inFixup = 0; L.dTeamWin = NULL; L.teamCap = 0; }
+  c->cfg = *cfg;
   Params &P = c->hp; memset(&P, 0, sizeof(P));
   P.width = cfg->width; P.height = cfg->height; P.bitDepth = cfg->bit_depth; P.wpp = cfg->wavefront_synchro;
   P.wCtu = (cfg->width + 63) / 64; P.hCtu = (cfg->height + 63) / 64;
   P.stride[0] = P.wCtu * 64; P.stride[1] = P.stride[2] = P.wCtu * 32;
   c->numCtus = P.wCtu * P.hCtu;
   *out = c;   // from here on the caller destroys on failure
-  HM_CHECK(c, hipStreamCreate(&c->stream));
-  HM_CHECK(c, hipEventCreate(&c->ev0)); HM_CHECK(c, hipEventCreate(&c->ev1));
+  { const int rc = lane_init(c, 0); if (rc != HM355_OK) return rc; }
   Tables *ht = new Tables; hm355_build_tables(ht);
-  hipError_t e = hipMalloc((void **)&c->dTab, sizeof(Tables));
+  hipError_t e = c->dTab.alloc(1);
   if (e == hipSuccess) e = hipMemcpy(c->dTab, ht, sizeof(Tables), hipMemcpyHostToDevice);
   delete ht;
   HM_CHECK(c, e);
-  // one scratch area per resident workgroup of the persistent grid: 256 CUs x 8 single-wave workgroups, or fewer when the batch is small
-  c->wsCount = (size_t)c->numCtus * (size_t)cfg->max_batch * HM_TEAM; if (c->wsCount > 3072) c->wsCount = 3072;   // 12 searches per CU x 256 CUs is the most that can be resident; a small batch runs as teams of HM_TEAM wavefronts per CTU
-  HM_CHECK(c, hipMalloc((void **)&c->dSched, 64)); HM_CHECK(c, hipMemset(c->dSched, 0, 64));
-  HM_CHECK(c, hipMalloc((void **)&c->dWs, c->wsCount * sizeof(WorkSpace)));
-  HM_CHECK(c, hipMalloc((void **)&c->dFrames, sizeof(FrameBuf) * cfg->max_batch));
-  HM_CHECK(c, hipMalloc((void **)&c->dP, sizeof(Params)));
+  HM_CHECK(c, c->dFrames.alloc(cfg->max_batch));
   c->slots.resize(cfg->max_batch);
   { // the pictures' buffers come out of ONE allocation (a batch of thousands of small pictures used to mean tens of thousands of hipMallocs)
     size_t planeBytes[3], off = 0;
-    for (int k = 0; k < 3; k++) planeBytes[k] = ((size_t)P.stride[k] * P.hCtu * (k ? 32 : 64) * sizeof(Pel) + 255) & ~(size_t)255;
-    const size_t metaBytes = (sizeof(CtuMeta) * c->numCtus + 255) & ~(size_t)255, coefBytes = (sizeof(TCoeff) * (size_t)c->numCtus * HM_COEF_CTU + 255) & ~(size_t)255;
-    const size_t statBytes = (sizeof(CtuStat) * c->numCtus + 255) & ~(size_t)255, endBytes = (sizeof(Cabac) * c->numCtus + 255) & ~(size_t)255;
-    const size_t doneBytes = (sizeof(uint32_t) * c->numCtus + 255) & ~(size_t)255;
+    for (int k = 0; k < 3; k++) planeBytes[k] = align256((size_t)P.stride[k] * P.hCtu * (k ? 32 : 64) * sizeof(Pel));
+    const size_t metaBytes = align256(sizeof(CtuMeta) * c->numCtus), coefBytes = align256(sizeof(TCoeff) * (size_t)c->numCtus * HM_COEF_CTU);
+    const size_t statBytes = align256(sizeof(CtuStat) * c->numCtus), endBytes = align256(sizeof(Cabac) * c->numCtus);
+    const size_t doneBytes = align256(sizeof(uint32_t) * c->numCtus);
     const size_t slotBytes = 2 * (planeBytes[0] + planeBytes[1] + planeBytes[2]) + metaBytes + coefBytes + statBytes + endBytes + doneBytes;
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess && slotBytes * (size_t)cfg->max_batch > freeB) {
       c->err = "hm355_create: max_batch pictures of this size do not fit the device memory"; return HM355_ERR_NOMEM; }
-    HM_CHECK(c, hipMalloc((void **)&c->arena, slotBytes * (size_t)cfg->max_batch));
+    HM_CHECK(c, c->arena.alloc(slotBytes * (size_t)cfg->max_batch));
     HM_CHECK(c, hipMemset(c->arena, 0, slotBytes * (size_t)cfg->max_batch));      // planes (padding included) and the done words start at zero
     for (int s = 0; s < cfg->max_batch; s++) {
-      FrameBuf &fb = c->slots[s].fb; memset(&fb, 0, sizeof(fb));
-      c->slots[s].imeta = NULL; c->slots[s].saoSrc[0] = c->slots[s].saoSrc[1] = c->slots[s].saoSrc[2] = NULL; c->slots[s].saoStat = NULL; c->slots[s].saoCand = NULL; c->slots[s].saoCoded = c->slots[s].saoRecon = NULL;
-      c->slots[s].rawIn = c->slots[s].rawOut = NULL;
-      c->slots[s].bitsRaw = c->slots[s].bitsPacked = NULL; c->slots[s].bitsSizes = NULL; c->slots[s].bitsSync = NULL; c->slots[s].bitsFlag = NULL; c->slots[s].bitsIp = NULL;
-      c->slots[s].dDqp = NULL; c->slots[s].dCtuQp = NULL; c->slots[s].dDqpOut = NULL; c->slots[s].dRowFlag = NULL; c->slots[s].dqpOn = 0; c->slots[s].dqpFlagIn = 0;
+      FrameBuf &fb = c->slots[s].fb;
       uint8_t *p = c->arena + off;
       for (int k = 0; k < 3; k++) { fb.org[k] = (Pel *)p; p += planeBytes[k]; fb.rec[k] = (Pel *)p; p += planeBytes[k]; }
       fb.meta = (CtuMeta *)p; p += metaBytes; fb.coef = (TCoeff *)p; p += coefBytes; fb.stat = (CtuStat *)p; p += statBytes;
@@ -310,58 +360,49 @@ extern "C" int hm355_create(const hm355_seq_cfg *cfg, hm355_ctx **out)
       off += slotBytes;
     }
   }
-  P.tab = c->dTab; P.ws = c->dWs; P.frames = c->dFrames; P.prof = NULL;
+  P.tab = c->dTab; P.ws = c->lane[0].dWs; P.frames = c->dFrames;
 #ifdef HM355_PROFILE
-  HM_CHECK(c, hipMalloc((void **)&P.prof, 2 * HM_PROF_N * sizeof(unsigned long long))); HM_CHECK(c, hipMemset(P.prof, 0, 2 * HM_PROF_N * sizeof(unsigned long long)));
+  HM_CHECK(c, c->prof.alloc(2 * HM_PROF_N)); HM_CHECK(c, hipMemset(c->prof, 0, 2 * HM_PROF_N * sizeof(unsigned long long)));
+  P.prof = c->prof;
 #elif defined(HM355_TRACE)
-  HM_CHECK(c, hipMalloc((void **)&P.prof, (1 + 3 * (size_t)HM_TRACE_CAP) * sizeof(unsigned long long))); HM_CHECK(c, hipMemset(P.prof, 0, sizeof(unsigned long long)));
+  HM_CHECK(c, c->prof.alloc(1 + 3 * (size_t)HM_TRACE_CAP)); HM_CHECK(c, hipMemset(c->prof, 0, sizeof(unsigned long long)));
+  P.prof = c->prof;
 #endif
-  HM_CHECK(c, hipMemcpy(c->dP, &P, sizeof(Params), hipMemcpyHostToDevice));
+  HM_CHECK(c, hipMemcpy(c->lane[0].dP, &P, sizeof(Params), hipMemcpyHostToDevice));
+  c->lane[0].fewWaves = P.fewWaves;
   return HM355_OK;
 }
 
 extern "C" void hm355_destroy(hm355_ctx *c)
 {
   if (!c) return;
-  for (size_t s = 0; s < c->slots.size(); s++) {
-    if (c->slots[s].imeta) hipFree(c->slots[s].imeta);
-    for (int k = 0; k < 3; k++) if (c->slots[s].saoSrc[k]) hipFree(c->slots[s].saoSrc[k]);
-    { Slot &sl = c->slots[s]; if (sl.rawIn) hipFree(sl.rawIn); if (sl.rawOut) hipFree(sl.rawOut); if (sl.bitsRaw) hipFree(sl.bitsRaw); if (sl.bitsPacked) hipFree(sl.bitsPacked); if (sl.bitsSizes) hipFree(sl.bitsSizes);
-      if (sl.bitsSync) hipFree(sl.bitsSync); if (sl.bitsFlag) hipFree(sl.bitsFlag); if (sl.bitsIp) hipFree(sl.bitsIp); }
-    { Slot &sl = c->slots[s]; if (sl.dDqp) hipFree(sl.dDqp); if (sl.dCtuQp) hipFree(sl.dCtuQp); if (sl.dDqpOut) hipFree(sl.dDqpOut); if (sl.dRowFlag) hipFree(sl.dRowFlag); }
-    if (c->slots[s].saoStat) hipFree(c->slots[s].saoStat); if (c->slots[s].saoCand) hipFree(c->slots[s].saoCand); if (c->slots[s].saoCoded) hipFree(c->slots[s].saoCoded); if (c->slots[s].saoRecon) hipFree(c->slots[s].saoRecon);
-  }
-  for (int l = 0; l < HM_MAX_LANES; l++) {
-    Lane &L = c->lane[l];
-    if (L.busy && L.stream) hipStreamSynchronize(L.stream);
-    if (L.dItems) hipFree(L.dItems);
-    if (L.dTeamWin) hipFree(L.dTeamWin);
-    if (l == 0) continue;           // lane 0 wraps the context's own objects, released below
-    if (L.dWs) hipFree(L.dWs); if (L.dSched) hipFree(L.dSched); if (L.dP) hipFree(L.dP);
-    if (L.ev0) hipEventDestroy(L.ev0); if (L.ev1) hipEventDestroy(L.ev1); if (L.stream) hipStreamDestroy(L.stream);
-  }
-  if (c->arena) hipFree(c->arena);
-  if (c->hStage) (void)hipHostFree(c->hStage);
-  if (c->dTab) hipFree(c->dTab); if (c->dWs) hipFree(c->dWs); if (c->dFrames) hipFree(c->dFrames); if (c->dP) hipFree(c->dP); if (c->dSched) hipFree(c->dSched);
-  if (c->staging) hipHostFree(c->staging);
-  if (c->dDbk) hipFree(c->dDbk);
-  if (c->dSao) hipFree(c->dSao);
-  if (c->dBits) hipFree(c->dBits);
-  if (c->dIngest) hipFree(c->dIngest);
-  if (c->ev0) hipEventDestroy(c->ev0); if (c->ev1) hipEventDestroy(c->ev1); if (c->stream) hipStreamDestroy(c->stream);
+  for (int l = 0; l < HM_MAX_LANES; l++) if (c->lane[l].busy) (void)hipStreamSynchronize(c->lane[l].stream);
   delete c;
+}
+
+// The visible area of the three planes between a slot's planes (padded to whole CTUs) and host planes of 2-byte samples, row after row:
+// asynchronous copies on lane 0's stream (the caller waits), or blocking ones
+static hipError_t copy_planes(hm355_ctx *c, Pel *const dev[3], uint16_t *const host[3], hipMemcpyKind kind, bool async)
+{
+  const Params &P = c->hp;
+  const bool up = kind == hipMemcpyHostToDevice;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && e == hipSuccess; k++) {
+    const int w = P.width >> (k ? 1 : 0), h = P.height >> (k ? 1 : 0);
+    const size_t devPitch = (size_t)P.stride[k] * sizeof(Pel), hostPitch = (size_t)w * 2;
+    void *dst = up ? (void *)dev[k] : (void *)host[k]; const void *src = up ? (const void *)host[k] : (const void *)dev[k];
+    const size_t dpitch = up ? devPitch : hostPitch, spitch = up ? hostPitch : devPitch;
+    e = async ? hipMemcpy2DAsync(dst, dpitch, src, spitch, hostPitch, h, kind, c->lane[0].stream) : hipMemcpy2D(dst, dpitch, src, spitch, hostPitch, h, kind);
+  }
+  return e;
 }
 
 extern "C" int hm355_upload(hm355_ctx *c, int slot, const hm355_planes *org)
 {
   if (!c || !org || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
-  const Params &P = c->hp; FrameBuf &fb = c->slots[slot].fb;
-  for (int k = 0; k < 3; k++) {
-    if (!org->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
-    const int w = P.width >> (k ? 1 : 0), h = P.height >> (k ? 1 : 0);
-    HM_CHECK(c, hipMemcpy2DAsync(fb.org[k], (size_t)P.stride[k] * sizeof(Pel), org->plane[k], (size_t)w * 2, (size_t)w * 2, h, hipMemcpyHostToDevice, c->stream));
-  }
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 3; k++) if (!org->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
+  HM_CHECK(c, copy_planes(c, c->slots[slot].fb.org, org->plane, hipMemcpyHostToDevice, true));
+  HM_CHECK(c, hipStreamSynchronize(c->lane[0].stream));
   return HM355_OK;
 }
 
@@ -372,10 +413,8 @@ static int dqp_prepare(hm355_ctx *c, int slot, const hm355_slice_desc *sd, hipSt
   Slot &sl = c->slots[slot]; const Params &P = c->hp;
   sl.lastSlice = *sd;
   if (!sl.dqpOn) { sl.fb.dqp = NULL; return HM355_OK; }
-  if (!sl.dDqp) {
-    HM_CHECK(c, hipMalloc((void **)&sl.dDqp, sizeof(DqpPic))); HM_CHECK(c, hipMalloc((void **)&sl.dCtuQp, c->numCtus));
-    HM_CHECK(c, hipMalloc((void **)&sl.dDqpOut, sizeof(CtuDqp) * c->numCtus)); HM_CHECK(c, hipMalloc((void **)&sl.dRowFlag, P.hCtu));
-  }
+  HM_CHECK(c, sl.dDqp.ensure(1)); HM_CHECK(c, sl.dCtuQp.ensure(c->numCtus));
+  HM_CHECK(c, sl.dDqpOut.ensure(c->numCtus)); HM_CHECK(c, sl.dRowFlag.ensure(P.hCtu));
   DqpPic *hp = new DqpPic; memset(hp, 0, sizeof(*hp));
   hp->flagIn = sl.dqpFlagIn; hp->sliceQp = sd->qp; hp->ctuQp = sl.dCtuQp; hp->out = sl.dDqpOut; hp->rowFlag = sl.dRowFlag;
   for (int q = -12; q <= 51; q++) {
@@ -396,29 +435,13 @@ static int dqp_prepare(hm355_ctx *c, int slot, const hm355_slice_desc *sd, hipSt
   return HM355_OK;
 }
 
-// Lane l of the context: lane 0 wraps the context's own stream, scratch areas and scheduler words; further lanes get theirs on first use.
-static int lane_prepare(hm355_ctx *c, int l)
-{
-  Lane &L = c->lane[l];
-  if (L.stream) return HM355_OK;
-  if (l == 0) { L.stream = c->stream; L.ev0 = c->ev0; L.ev1 = c->ev1; L.dP = c->dP; L.dWs = c->dWs; L.wsCount = c->wsCount; L.dSched = c->dSched; L.fewWaves = c->hp.fewWaves; return HM355_OK; }
-  HM_CHECK(c, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-  HM_CHECK(c, hipEventCreate(&L.ev0)); HM_CHECK(c, hipEventCreate(&L.ev1));
-  L.wsCount = c->wsCount;
-  HM_CHECK(c, hipMalloc((void **)&L.dWs, L.wsCount * sizeof(WorkSpace)));
-  HM_CHECK(c, hipMalloc((void **)&L.dSched, 64)); HM_CHECK(c, hipMemset(L.dSched, 0, 64));
-  HM_CHECK(c, hipMalloc((void **)&L.dP, sizeof(Params)));
-  L.fewWaves = -1;
-  return HM355_OK;
-}
-
 // Enqueues the search over CTU rows [row0, row1] of the pictures in slots [slot0, slot0 + n) on lane l and returns; rows above row0 hold
 // finished (or imported) CTUs.  Launches of different lanes run concurrently (each on its own stream with its own scratch areas), so the
 // drain of one step overlaps the fill of the next; their slot ranges must not overlap.
 static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_desc *slices, int row0, int row1)
 {
   const Params &P = c->hp;
-  int rc = lane_prepare(c, l);
+  int rc = lane_init(c, l);
   if (rc != HM355_OK) return rc;
   Lane &L = c->lane[l];
   if (L.busy) return fail(c, HM355_ERR_ARG, "hm355_run_begin: the lane still has a launch in flight (hm355_run_wait first)");
@@ -437,12 +460,7 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   if (!L.keyValid || memcmp(key, L.key, sizeof(key)) != 0) {
     L.keyValid = 0;
     hm355_build_schedule(P.wCtu, P.hCtu, P.wpp, n, L.items, L.stepStart, carry, slot0, row0, row1);
-    if (L.items.size() > L.itemsCap) {
-      if (L.dItems) hipFree(L.dItems);
-      L.dItems = NULL; L.itemsCap = 0;
-      HM_CHECK(c, hipMalloc((void **)&L.dItems, sizeof(WorkItem) * L.items.size()));
-      L.itemsCap = L.items.size();
-    }
+    HM_CHECK(c, L.dItems.grow(L.items.size()));
     HM_CHECK(c, hipMemcpyAsync(L.dItems, L.items.data(), sizeof(WorkItem) * L.items.size(), hipMemcpyHostToDevice, L.stream));
     memcpy(L.key, key, sizeof(key)); L.keyValid = 1;
   }
@@ -454,10 +472,11 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   // 798 / 1,556, 64: 1,538 / 2,356, 128: 2,862 / 2,944 -- teams up to 96 streams (1,024 when every stream is one serial chain of CTUs).
   const long long parallel = (long long)n * (P.wpp ? 16 : 1);
   const int fewWaves = parallel < 1280 ? 1 : 0;
+  const size_t wsCount = L.dWs.n;
   int anyInter = 0;
   for (int f = 0; f < n; f++) if (c->slots[slot0 + f].fb.imeta) anyInter = 1;
-  int useTeam = (anyInter ? (P.wpp ? n <= 96 : n <= 1024) : parallel <= 512) && L.wsCount >= HM_TEAM;
-  { const char *ev = getenv("HM355_TEAM"); if (ev && ev[0] == '0') useTeam = 0; if (ev && ev[0] == '1' && L.wsCount >= HM_TEAM) useTeam = 1; }
+  int useTeam = (anyInter ? (P.wpp ? n <= 96 : n <= 1024) : parallel <= 512) && wsCount >= HM_TEAM;
+  { const char *ev = getenv("HM355_TEAM"); if (ev && ev[0] == '0') useTeam = 0; if (ev && ev[0] == '1' && wsCount >= HM_TEAM) useTeam = 1; }
   const size_t winSamples = (size_t)65 * P.stride[0] + (size_t)33 * (P.stride[1] + P.stride[2]);
   int teams = 0;
   int waves = anyInter ? HM_TEAM : HM_TEAM_I;   // P / B slices: every chain of candidates on two or three wavefronts (hm355_team.h)
@@ -466,12 +485,11 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     const size_t total = L.items.size();
     // as many teams as CTUs can ever be ready at once (the wavefront's widest step), a few more so that a finished team finds the next ticket taken
     size_t want = (size_t)maxItemsPerStep(P.wCtu, row1 - row0 + 1 < P.hCtu ? row1 - row0 + 1 : P.hCtu, P.wpp, n) + 2;
-    if (want > total) want = total; if (want > 512) want = 512; if (want > L.wsCount / waves) want = L.wsCount / waves;
-    if (want > L.teamCap) {
+    if (want > total) want = total; if (want > 512) want = 512; if (want > wsCount / waves) want = wsCount / waves;
+    if (want > L.teamCap) {   // the windows grow only after the lane's stream is idle; without them the launch runs without teams
       HM_CHECK(c, hipStreamSynchronize(L.stream));
-      if (L.dTeamWin) hipFree(L.dTeamWin);
-      L.dTeamWin = NULL; L.teamCap = 0; L.fewWaves = -1;
-      if (hipMalloc((void **)&L.dTeamWin, want * HM_TEAM_HELPERS * winSamples * sizeof(Pel)) != hipSuccess) { (void)hipGetLastError(); useTeam = 0; }
+      L.teamCap = 0; L.fewWaves = -1;
+      if (L.dTeamWin.alloc(want * HM_TEAM_HELPERS * winSamples) != hipSuccess) { (void)hipGetLastError(); useTeam = 0; }
       else L.teamCap = want;
     }
     teams = (int)(want < L.teamCap ? want : L.teamCap);
@@ -483,7 +501,7 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     HM_CHECK(c, hipStreamSynchronize(L.stream));      // lp is a local
     L.fewWaves = fewWaves;
   }
-  c->epoch++; if (c->epoch == 0) c->epoch = 1;
+  next_epoch(c);
   HM_CHECK(c, hipMemsetAsync(L.dSched, 0, 32, L.stream));       // ticket = 0, abort = 0, published CTUs = 0 (+ the counters of diagnostic builds)
   if (row0 > 0)    // the row above the band is complete: its CTUs count as published in this run
     for (int f = 0; f < n; f++) HM_CHECK(c, hipMemsetD32Async((hipDeviceptr_t)(c->slots[slot0 + f].fb.done + (size_t)(row0 - 1) * P.wCtu), (int)c->epoch, P.wCtu, L.stream));
@@ -495,14 +513,14 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     if (!c->teamLdsSet) { HM_CHECK(c, hipFuncSetAttribute((const void *)hm355_ctu_team_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HM_TEAM_LDS_BYTES(HM_TEAM))); c->teamLdsSet = 1; }
     hipLaunchKernelGGL(hm355_ctu_team_kernel, dim3(L.grid), dim3(64 * waves), lds, L.stream, (const Params *)L.dP, (const WorkItem *)L.dItems, total, L.dSched, c->epoch);
   } else {
-    L.grid = total < (int)L.wsCount ? total : (int)L.wsCount;
+    L.grid = total < (int)wsCount ? total : (int)wsCount;
     // A caller that keeps `share` launches in flight (hm355_set_lane_share): each launch only takes its share of the searches the device can hold --
     // a persistent workgroup that waits for a neighbouring CTU keeps its place on the CU, so a launch sized for the whole device would lock the
     // others out until its tickets run out, and the launches would run one after the other
     if (c->laneShare > 1) { const int cap = (int)(3072 * 5 / (4 * c->laneShare)); if (L.grid > cap) L.grid = cap; }
     // workgroups of HM_CTU_WAVES independent searches (wavefronts); a search's workspace is blockIdx * HM_CTU_WAVES + wave < wsCount
     int groups = (L.grid + HM_CTU_WAVES - 1) / HM_CTU_WAVES;
-    if (groups > (int)(L.wsCount / HM_CTU_WAVES)) groups = (int)(L.wsCount / HM_CTU_WAVES);
+    if (groups > (int)(wsCount / HM_CTU_WAVES)) groups = (int)(wsCount / HM_CTU_WAVES);
     L.grid = groups * HM_CTU_WAVES;
     hipLaunchKernelGGL(hm355_ctu_kernel, dim3(groups), dim3(64 * HM_CTU_WAVES), 0, L.stream, (const Params *)L.dP, (const WorkItem *)L.dItems, total, L.dSched, c->epoch);
   }
@@ -511,7 +529,6 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   L.busy = 1;
   return HM355_OK;
 }
-static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_desc *slices, int row0, int row1);
 static int run_wait(hm355_ctx *c, int l, double *kernelMs);
 // WaveFrontSynchro with cu_qp_delta: TEncCu::m_bEncodeDQP reaches the first CTU of a row from the LAST CTU of the row above (coding order), which the
 // wavefront has not searched yet when that row starts.  The launch ran on an assumption per row (Slot::rowFlag, "clear" to begin with: a CTU with
@@ -596,6 +613,31 @@ extern "C" int hm355_run_wait(hm355_ctx *c, int lane, double *kernel_ms)
   return run_wait(c, lane, kernel_ms);
 }
 
+// A timed group of launches on lane 0's stream: ev0, what `enqueue` puts on the stream (it returns the first error), ev1, one wait.  The time
+// and the number of launches are what hm355_last_run_info reports.
+template <class F> static int timed_launches(hm355_ctx *c, int launches, F enqueue)
+{
+  Lane &L = c->lane[0];
+  HM_CHECK(c, hipEventRecord(L.ev0, L.stream));
+  HM_CHECK(c, enqueue(L.stream));
+  HM_CHECK(c, hipEventRecord(L.ev1, L.stream));
+  HM_CHECK(c, hipStreamSynchronize(L.stream));
+  float ms = 0; HM_CHECK(c, hipEventElapsedTime(&ms, L.ev0, L.ev1));
+  c->lastKernelMs = ms; c->lastLaunches = launches;
+  return HM355_OK;
+}
+// The FrameBufs of slots 0..n-1 (fbs, n = fbs.size()) and one parameter block per picture (into dst: [max_batch], allocated on first use) go
+// to the device for a pass over the slots; returns once they are there.
+template <class T> static int stage_slots(hm355_ctx *c, const std::vector<FrameBuf> &fbs, DevBuf<T> &dst, const std::vector<T> &params)
+{
+  const hipStream_t s = c->lane[0].stream;
+  HM_CHECK(c, dst.ensure(c->slots.size()));
+  HM_CHECK(c, hipMemcpyAsync(c->dFrames, fbs.data(), sizeof(FrameBuf) * fbs.size(), hipMemcpyHostToDevice, s));
+  HM_CHECK(c, hipMemcpyAsync(dst, params.data(), sizeof(T) * fbs.size(), hipMemcpyHostToDevice, s));
+  HM_CHECK(c, hipStreamSynchronize(s));
+  return HM355_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // cu_qp_delta: adaptive QP / rate control hooks of compressSlice
 // ------------------------------------------------------------------------------------------------
@@ -628,19 +670,16 @@ extern "C" int hm355_get_dqp(hm355_ctx *c, int slot, int8_t *qp_out, int32_t *dq
 extern "C" int hm355_preanalyze(hm355_ctx *c, int slot, uint64_t *sums)
 {
   if (!c || !sums || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
-  unsigned long long *d = NULL;
+  DevBuf<unsigned long long> d;
   HM_CHECK(c, hipMemcpy(c->dFrames + slot, &c->slots[slot].fb, sizeof(FrameBuf), hipMemcpyHostToDevice));
-  HM_CHECK(c, hipMalloc((void **)&d, sizeof(unsigned long long) * 8 * c->numCtus));
-  HM_CHECK(c, hipEventRecord(c->ev0, c->stream));
-  hipLaunchKernelGGL(hm355_preanalyze_kernel, dim3(c->numCtus), dim3(64), 0, c->stream, (const Params *)c->dP, slot, d);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipMemcpy(sums, d, sizeof(unsigned long long) * 8 * c->numCtus, hipMemcpyDeviceToHost);
-  hipFree(d);
-  HM_CHECK(c, e);
-  float ms = 0; HM_CHECK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->lastKernelMs = ms; c->lastLaunches = 1;
+  HM_CHECK(c, d.alloc((size_t)8 * c->numCtus));
+  const Params *dP = c->lane[0].dP;
+  const int rc = timed_launches(c, 1, [&](hipStream_t s) {
+    hipLaunchKernelGGL(hm355_preanalyze_kernel, dim3(c->numCtus), dim3(64), 0, s, dP, slot, d.p);
+    return hipGetLastError();
+  });
+  if (rc != HM355_OK) return rc;
+  HM_CHECK(c, hipMemcpy(sums, d, sizeof(unsigned long long) * d.n, hipMemcpyDeviceToHost));
   return HM355_OK;
 }
 
@@ -717,49 +756,51 @@ extern "C" int hm355_last_run_info(const hm355_ctx *c, double *kernel_ms, int *l
   return HM355_OK;
 }
 
+// One CTU as the C ABI carries it (hm355_ctu_out) and as the device holds it (CtuStat, CtuMeta and HM_COEF_CTU coefficients: Y at 0, Cb at
+// 4096, Cr at 5120)
+static void ctu_to_out(const CtuStat &st, const CtuMeta &m, const TCoeff *cf, hm355_ctu_out *o)
+{
+  o->total_cost = st.cost; o->total_bits = st.bits; o->total_dist = st.dist;
+  memcpy(o->depth, m.depth, 256); memcpy(o->part_size, m.part, 256); memcpy(o->pred_mode, m.pred, 256);
+  memcpy(o->intra_dir_luma, m.dirL, 256); memcpy(o->intra_dir_chroma, m.dirC, 256); memcpy(o->tr_idx, m.tr, 256);
+  memcpy(o->cbf, m.cbf, 768); memcpy(o->tskip, m.ts, 768);
+  memcpy(o->coeff_y, cf, 4096 * 4); memcpy(o->coeff_cb, cf + 4096, 1024 * 4); memcpy(o->coeff_cr, cf + 5120, 1024 * 4);
+}
+static void ctu_from_out(const hm355_ctu_out &o, CtuMeta *m, TCoeff *cf)   // cf NULL: the CU / TU data only
+{
+  memcpy(m->depth, o.depth, 256); memcpy(m->part, o.part_size, 256); memcpy(m->pred, o.pred_mode, 256);
+  memcpy(m->dirL, o.intra_dir_luma, 256); memcpy(m->dirC, o.intra_dir_chroma, 256); memcpy(m->tr, o.tr_idx, 256);
+  memcpy(m->cbf, o.cbf, 768); memcpy(m->ts, o.tskip, 768);
+  if (cf) { memcpy(cf, o.coeff_y, 4096 * 4); memcpy(cf + 4096, o.coeff_cb, 1024 * 4); memcpy(cf + 5120, o.coeff_cr, 1024 * 4); }
+}
+
 extern "C" int hm355_download(hm355_ctx *c, int slot, hm355_planes *rec, hm355_ctu_out *ctus, hm355_slice_stats *stats)
 {
   if (!c || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
-  const Params &P = c->hp; FrameBuf &fb = c->slots[slot].fb;
+  const Params &P = c->hp; FrameBuf &fb = c->slots[slot].fb; const hipStream_t s = c->lane[0].stream;
   if (rec) for (int k = 0; k < 3; k++) if (!rec->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
   // one picture's results cross PCIe into a pinned staging buffer (asynchronous copies on the context's stream, one wait), then go to the caller's
   // pageable buffers with plain memcpy: 81 MB per 4K picture
   const size_t nC = (size_t)c->numCtus, bStat = sizeof(CtuStat) * nC, bMeta = sizeof(CtuMeta) * nC, bCoef = sizeof(TCoeff) * nC * HM_COEF_CTU;
-  size_t bPlane[3], oPlane[3], off = (bStat + bMeta + bCoef + 255) & ~(size_t)255;
-  for (int k = 0; k < 3; k++) { bPlane[k] = (size_t)(P.width >> (k ? 1 : 0)) * 2 * (size_t)(P.height >> (k ? 1 : 0)); oPlane[k] = off; off += (bPlane[k] + 255) & ~(size_t)255; }
-  if (c->hStageBytes < off) {
-    if (c->hStage) (void)hipHostFree(c->hStage);
-    c->hStage = NULL; c->hStageBytes = 0;
-    HM_CHECK(c, hipHostMalloc((void **)&c->hStage, off, hipHostMallocDefault));
-    c->hStageBytes = off;
-  }
-  CtuStat *st = (CtuStat *)c->hStage; CtuMeta *meta = (CtuMeta *)(c->hStage + bStat); TCoeff *coef = (TCoeff *)(c->hStage + bStat + bMeta);
-  if (rec)
-    for (int k = 0; k < 3; k++) {
-      const int w = P.width >> (k ? 1 : 0), h = P.height >> (k ? 1 : 0);
-      HM_CHECK(c, hipMemcpy2DAsync(c->hStage + oPlane[k], (size_t)w * 2, fb.rec[k], (size_t)P.stride[k] * sizeof(Pel), (size_t)w * 2, h, hipMemcpyDeviceToHost, c->stream));
-    }
-  if (ctus || stats) HM_CHECK(c, hipMemcpyAsync(st, fb.stat, bStat, hipMemcpyDeviceToHost, c->stream));
+  size_t bPlane[3], oPlane[3], off = align256(bStat + bMeta + bCoef);
+  for (int k = 0; k < 3; k++) { bPlane[k] = (size_t)(P.width >> (k ? 1 : 0)) * 2 * (size_t)(P.height >> (k ? 1 : 0)); oPlane[k] = off; off += align256(bPlane[k]); }
+  HM_CHECK(c, c->hStage.grow(off));
+  unsigned char *hs = c->hStage.p;
+  CtuStat *st = (CtuStat *)hs; CtuMeta *meta = (CtuMeta *)(hs + bStat); TCoeff *coef = (TCoeff *)(hs + bStat + bMeta);
+  uint16_t *const stagedPlanes[3] = { (uint16_t *)(hs + oPlane[0]), (uint16_t *)(hs + oPlane[1]), (uint16_t *)(hs + oPlane[2]) };
+  if (rec) HM_CHECK(c, copy_planes(c, fb.rec, stagedPlanes, hipMemcpyDeviceToHost, true));
+  if (ctus || stats) HM_CHECK(c, hipMemcpyAsync(st, fb.stat, bStat, hipMemcpyDeviceToHost, s));
   if (ctus) {
-    HM_CHECK(c, hipMemcpyAsync(meta, fb.meta, bMeta, hipMemcpyDeviceToHost, c->stream));
-    HM_CHECK(c, hipMemcpyAsync(coef, fb.coef, bCoef, hipMemcpyDeviceToHost, c->stream));
+    HM_CHECK(c, hipMemcpyAsync(meta, fb.meta, bMeta, hipMemcpyDeviceToHost, s));
+    HM_CHECK(c, hipMemcpyAsync(coef, fb.coef, bCoef, hipMemcpyDeviceToHost, s));
   }
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  if (rec) for (int k = 0; k < 3; k++) memcpy(rec->plane[k], c->hStage + oPlane[k], bPlane[k]);
+  HM_CHECK(c, hipStreamSynchronize(s));
+  if (rec) for (int k = 0; k < 3; k++) memcpy(rec->plane[k], stagedPlanes[k], bPlane[k]);
   if (stats) {
     stats->pic_total_bits = 0; stats->pic_rd_cost = 0; stats->pic_dist = 0;
     for (int a = 0; a < c->numCtus; a++) { stats->pic_total_bits += st[a].bits; stats->pic_rd_cost += st[a].cost; stats->pic_dist += st[a].dist; }
   }
-  if (ctus)
-    for (int a = 0; a < c->numCtus; a++) {
-      hm355_ctu_out *o = ctus + a; const CtuMeta *m = &meta[a];
-      o->total_cost = st[a].cost; o->total_bits = st[a].bits; o->total_dist = st[a].dist;
-      memcpy(o->depth, m->depth, 256); memcpy(o->part_size, m->part, 256); memcpy(o->pred_mode, m->pred, 256);
-      memcpy(o->intra_dir_luma, m->dirL, 256); memcpy(o->intra_dir_chroma, m->dirC, 256); memcpy(o->tr_idx, m->tr, 256);
-      memcpy(o->cbf, m->cbf, 768); memcpy(o->tskip, m->ts, 768);
-      const TCoeff *cf = coef + (size_t)a * HM_COEF_CTU;
-      memcpy(o->coeff_y, cf, 4096 * 4); memcpy(o->coeff_cb, cf + 4096, 1024 * 4); memcpy(o->coeff_cr, cf + 5120, 1024 * 4);
-    }
+  if (ctus) for (int a = 0; a < c->numCtus; a++) ctu_to_out(st[a], meta[a], coef + (size_t)a * HM_COEF_CTU, ctus + a);
   return HM355_OK;
 }
 
@@ -787,28 +828,37 @@ extern "C" int hm355_compress_slice(hm355_ctx *c, const hm355_slice_desc *slice,
 // of one call are independent of each other (e.g. the current pictures of n streams) and run concurrently
 // ------------------------------------------------------------------------------------------------
 static_assert(sizeof(hm355_ctu_inter_out) == sizeof(InterMeta), "hm355_ctu_inter_out mirrors InterMeta");
-namespace {
-struct DevAllocs {                     // device allocations that live for one call
-  std::vector<void *> p;
-  ~DevAllocs() { for (size_t i = 0; i < p.size(); i++) hipFree(p[i]); }
-  template <class T> hipError_t make(T **out, size_t count, const void *src)
-  {
-    *out = NULL;
-    hipError_t e = hipMalloc((void **)out, count * sizeof(T));
-    if (e != hipSuccess) return e;
-    p.push_back(*out);
-    return src ? hipMemcpy(*out, src, count * sizeof(T), hipMemcpyHostToDevice) : hipMemset(*out, 0, count * sizeof(T));
+static void ref_buf_bytes(const hm355_ctx *c, size_t bytes[REF_NBUF])
+{
+  const size_t np = (size_t)c->numCtus * 256;
+  for (int k = 0; k < 3; k++) {
+    const int cw = c->hp.width >> (k ? 1 : 0), ch = c->hp.height >> (k ? 1 : 0), mg = HM_REF_MARGIN >> (k ? 1 : 0);
+    bytes[REF_Y + k] = (size_t)(cw + 2 * mg) * (ch + 2 * mg) * sizeof(Pel);
   }
-};
+  bytes[REF_PRED_MODE] = np; bytes[REF_MV0] = bytes[REF_MV1] = np * sizeof(MvD); bytes[REF_REF_IDX0] = bytes[REF_REF_IDX1] = np;
 }
-static hipError_t upload_ref_pic(hm355_ctx *c, const hm355_ref_pic *hp, DevAllocs &da, RefPicDev *out)
+// allocates the buffers of r (ref_buf_bytes) and points r->dev at them
+static hipError_t ref_alloc(hm355_ctx *c, hm355_ref *r)
+{
+  size_t bytes[REF_NBUF]; ref_buf_bytes(c, bytes);
+  for (int i = 0; i < REF_NBUF; i++) { const hipError_t e = r->buf[i].alloc(bytes[i]); if (e != hipSuccess) return e; }
+  for (int k = 0; k < 3; k++) {
+    const int mg = HM_REF_MARGIN >> (k ? 1 : 0), st = (c->hp.width >> (k ? 1 : 0)) + 2 * mg;
+    r->dev.plane[k] = (const Pel *)r->buf[REF_Y + k].p + (size_t)mg * st + mg; r->dev.stride[k] = st;
+  }
+  r->dev.predMode = r->buf[REF_PRED_MODE];
+  r->dev.mv[0] = (const MvD *)r->buf[REF_MV0].p; r->dev.refIdx[0] = (const int8_t *)r->buf[REF_REF_IDX0].p;
+  r->dev.mv[1] = (const MvD *)r->buf[REF_MV1].p; r->dev.refIdx[1] = (const int8_t *)r->buf[REF_REF_IDX1].p;
+  return hipSuccess;
+}
+static hipError_t upload_ref_pic(hm355_ctx *c, const hm355_ref_pic *hp, hm355_ref *r)
 {
   const Params &P = c->hp;
-  RefPicDev r; memset(&r, 0, sizeof(r));
-  hipError_t e = hipSuccess;
+  size_t bytes[REF_NBUF]; ref_buf_bytes(c, bytes);
+  hipError_t e = ref_alloc(c, r);
   for (int cc = 0; cc < 3 && e == hipSuccess; cc++) {
-    const int cw = P.width >> (cc ? 1 : 0), ch = P.height >> (cc ? 1 : 0), mg = HM_REF_MARGIN >> (cc ? 1 : 0), st = cw + 2 * mg;
-    std::vector<Pel> buf((size_t)st * (ch + 2 * mg));
+    const int cw = P.width >> (cc ? 1 : 0), ch = P.height >> (cc ? 1 : 0), mg = HM_REF_MARGIN >> (cc ? 1 : 0), st = r->dev.stride[cc];
+    std::vector<Pel> buf(bytes[REF_Y + cc] / sizeof(Pel));
     for (int y = -mg; y < ch + mg; y++) {
       const int sy = y < 0 ? 0 : (y >= ch ? ch - 1 : y);
       Pel *d = buf.data() + (size_t)(y + mg) * st + mg;
@@ -816,20 +866,12 @@ static hipError_t upload_ref_pic(hm355_ctx *c, const hm355_ref_pic *hp, DevAlloc
       for (int x = 0; x < cw; x++) d[x] = (Pel)srow[x];
       for (int x = 1; x <= mg; x++) { d[-x] = (Pel)srow[0]; d[cw - 1 + x] = (Pel)srow[cw - 1]; }
     }
-    Pel *dv = NULL; e = da.make(&dv, buf.size(), buf.data());
-    r.plane[cc] = dv + (size_t)mg * st + mg; r.stride[cc] = st;
+    e = hipMemcpy(r->buf[REF_Y + cc], buf.data(), bytes[REF_Y + cc], hipMemcpyHostToDevice);
   }
-  const size_t np = (size_t)c->numCtus * 256;
-  uint8_t *dpm = NULL; if (e == hipSuccess) e = da.make(&dpm, np, hp->pred_mode);
-  r.predMode = dpm;
-  for (int l = 0; l < 2 && e == hipSuccess; l++) {
-    MvD *dm = NULL; int8_t *dr = NULL;
-    e = da.make(&dm, np, hp->mv[l]); if (e == hipSuccess) e = da.make(&dr, np, hp->ref_idx[l]);
-    r.mv[l] = dm; r.refIdx[l] = dr;
-    memcpy(r.refPoc[l], hp->ref_poc[l], sizeof(r.refPoc[l])); memcpy(r.refLT[l], hp->ref_lt[l], sizeof(r.refLT[l]));
-  }
-  r.poc = hp->poc; r.isLongTerm = hp->long_term;
-  *out = r;
+  const void *motion[REF_NBUF - REF_PRED_MODE] = { hp->pred_mode, hp->mv[0], hp->ref_idx[0], hp->mv[1], hp->ref_idx[1] };
+  for (int i = REF_PRED_MODE; i < REF_NBUF && e == hipSuccess; i++) e = hipMemcpy(r->buf[i], motion[i - REF_PRED_MODE], bytes[i], hipMemcpyHostToDevice);
+  for (int l = 0; l < 2; l++) { memcpy(r->dev.refPoc[l], hp->ref_poc[l], sizeof(r->dev.refPoc[l])); memcpy(r->dev.refLT[l], hp->ref_lt[l], sizeof(r->dev.refLT[l])); }
+  r->dev.poc = hp->poc; r->dev.isLongTerm = hp->long_term;
   return e;
 }
 extern "C" int hm355_compress_slices_inter(hm355_ctx *c, int n, const hm355_inter_slice_desc *slices, const hm355_planes *org,
@@ -853,9 +895,8 @@ extern "C" int hm355_compress_slices_inter(hm355_ctx *c, int n, const hm355_inte
   }
   int rc;
   for (int f = 0; f < n; f++) if ((rc = hm355_upload(c, f, org + f)) != HM355_OK) return rc;
-  DevAllocs da;
-  std::vector<const hm355_ref_pic *> seen; std::vector<RefPicDev> devRefs;     // a picture referenced several times is uploaded once
-  std::vector<InterMeta *> dIm(n, (InterMeta *)NULL);
+  std::vector<const hm355_ref_pic *> seen; std::vector<hm355_ref> uploaded;     // a picture referenced several times is uploaded once
+  std::vector<DevBuf<InterPic>> dIp(n); std::vector<DevBuf<MvD>> dIntMv(n);
   std::vector<hm355_slice_desc> base(n);
   hipError_t e = hipSuccess;
   for (int f = 0; f < n && e == hipSuccess; f++) {
@@ -869,27 +910,28 @@ extern "C" int hm355_compress_slices_inter(hm355_ctx *c, int n, const hm355_inte
       if (sd->dev_ref[l][i]) { hip.ref[l][i] = sd->dev_ref[l][i]->dev; continue; }
       const hm355_ref_pic *hp = sd->ref[l][i];
       size_t k = 0; for (; k < seen.size(); k++) if (seen[k] == hp) break;
-      if (k == seen.size()) { RefPicDev r; e = upload_ref_pic(c, hp, da, &r); seen.push_back(hp); devRefs.push_back(r); }
-      hip.ref[l][i] = devRefs[k];
+      if (k == seen.size()) { uploaded.emplace_back(); e = upload_ref_pic(c, hp, &uploaded.back()); seen.push_back(hp); }
+      hip.ref[l][i] = uploaded[k].dev;
     }
     for (int i1 = 0; i1 < sd->num_ref_idx[1]; i1++) {            // TComSlice::setList1IdxToList0Idx
       hip.list1ToList0[i1] = -1;
       for (int i0 = 0; i0 < sd->num_ref_idx[0]; i0++) if (hip.ref[0][i0].poc == hip.ref[1][i1].poc) { hip.list1ToList0[i1] = i0; break; }
     }
-    FrameBuf &fb = c->slots[f].fb;
-    InterPic *dIp = NULL; MvD *dIntMv = NULL;
-    if (e == hipSuccess) e = da.make(&dIp, 1, &hip);
-    if (e == hipSuccess && !c->slots[f].imeta) e = hipMalloc((void **)&c->slots[f].imeta, sizeof(InterMeta) * c->numCtus);
-    if (e == hipSuccess) { dIm[f] = c->slots[f].imeta; e = hipMemset(dIm[f], 0, sizeof(InterMeta) * c->numCtus); }
-    if (e == hipSuccess) e = da.make(&dIntMv, (size_t)c->numCtus * 32, NULL);
-    fb.imeta = dIm[f]; fb.ip = dIp; fb.intMv = dIntMv;
+    Slot &sl = c->slots[f];
+    if (e == hipSuccess) e = dIp[f].alloc(1);
+    if (e == hipSuccess) e = hipMemcpy(dIp[f], &hip, sizeof(InterPic), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = sl.imeta.ensure(c->numCtus);
+    if (e == hipSuccess) e = hipMemset(sl.imeta, 0, sizeof(InterMeta) * c->numCtus);
+    if (e == hipSuccess) e = dIntMv[f].alloc((size_t)c->numCtus * 32);
+    if (e == hipSuccess) e = hipMemset(dIntMv[f], 0, sizeof(MvD) * dIntMv[f].n);
+    sl.fb.imeta = sl.imeta; sl.fb.ip = dIp[f]; sl.fb.intMv = dIntMv[f];
     base[f] = sd->base; base[f].slice_type = 2;            // hm355_run validates the common fields
   }
   if (e != hipSuccess) { c->err = std::string("reference picture upload: ") + hipGetErrorString(e); rc = HM355_ERR_DEVICE; }
   else rc = hm355_run(c, n, base.data());
   for (int f = 0; f < n && rc == HM355_OK; f++) {
     rc = hm355_download(c, f, rec ? rec + f : NULL, ctus ? ctus[f] : NULL, stats ? stats + f : NULL);
-    if (rc == HM355_OK && ictus && ictus[f] && hipMemcpy(ictus[f], dIm[f], sizeof(InterMeta) * c->numCtus, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "motion download failed"; rc = HM355_ERR_DEVICE; }
+    if (rc == HM355_OK && ictus && ictus[f] && hipMemcpy(ictus[f], c->slots[f].imeta, sizeof(InterMeta) * c->numCtus, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "motion download failed"; rc = HM355_ERR_DEVICE; }
   }
   for (int f = 0; f < n; f++) { FrameBuf &fb = c->slots[f].fb; fb.imeta = NULL; fb.ip = NULL; fb.intMv = NULL; }
   return rc;
@@ -907,8 +949,6 @@ extern "C" int hm355_compress_slice_inter(hm355_ctx *c, const hm355_inter_slice_
 extern "C" void hm355_ref_release(hm355_ctx *c, hm355_ref *r)
 {
   (void)c;
-  if (!r) return;
-  for (size_t i = 0; i < r->owned.size(); i++) hipFree(r->owned[i]);
   delete r;
 }
 extern "C" int hm355_ref_from_slot(hm355_ctx *c, int slot, int32_t poc, int32_t is_inter, const int32_t num_ref[2], const int32_t ref_poc[2][16],
@@ -916,38 +956,29 @@ extern "C" int hm355_ref_from_slot(hm355_ctx *c, int slot, int32_t poc, int32_t 
 {
   if (!c || !out || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
   if (is_inter && !c->slots[slot].imeta) return fail(c, HM355_ERR_ARG, "hm355_ref_from_slot: the slot holds no motion data");
-  const Params &P = c->hp;
-  hm355_ref *r = new hm355_ref(); memset(&r->dev, 0, sizeof(r->dev));
-  FrameBuf fbh = c->slots[slot].fb; fbh.imeta = is_inter ? c->slots[slot].imeta : NULL;
+  const Params &P = c->hp; const hipStream_t s = c->lane[0].stream; const Params *dP = c->lane[0].dP;
+  std::unique_ptr<hm355_ref> r(new hm355_ref());
+  FrameBuf fbh = c->slots[slot].fb; fbh.imeta = is_inter ? c->slots[slot].imeta.p : NULL;
   hipError_t e = hipMemcpy(c->dFrames + slot, &fbh, sizeof(FrameBuf), hipMemcpyHostToDevice);
-  const size_t np = (size_t)c->numCtus * 256;
-  Pel *pl[3] = {NULL, NULL, NULL}; uint8_t *pm = NULL; MvD *mv[2] = {NULL, NULL}; int8_t *ri[2] = {NULL, NULL};
-  for (int k = 0; k < 3 && e == hipSuccess; k++) {
-    const int cw = P.width >> (k ? 1 : 0), ch = P.height >> (k ? 1 : 0), mg = HM_REF_MARGIN >> (k ? 1 : 0), st = cw + 2 * mg;
-    e = hipMalloc((void **)&pl[k], (size_t)st * (ch + 2 * mg) * sizeof(Pel));
-    if (e == hipSuccess) { r->owned.push_back(pl[k]); r->dev.plane[k] = pl[k] + (size_t)mg * st + mg; r->dev.stride[k] = st; }
-  }
-  if (e == hipSuccess) { e = hipMalloc((void **)&pm, np); if (e == hipSuccess) r->owned.push_back(pm); }
-  for (int l = 0; l < 2 && e == hipSuccess; l++) {
-    e = hipMalloc((void **)&mv[l], np * sizeof(MvD)); if (e == hipSuccess) r->owned.push_back(mv[l]);
-    if (e == hipSuccess) { e = hipMalloc((void **)&ri[l], np); if (e == hipSuccess) r->owned.push_back(ri[l]); }
-  }
+  if (e == hipSuccess) e = ref_alloc(c, r.get());
   if (e == hipSuccess) {
+    uint8_t *pm = r->buf[REF_PRED_MODE]; MvD *mv0 = (MvD *)r->buf[REF_MV0].p, *mv1 = (MvD *)r->buf[REF_MV1].p;
+    int8_t *ri0 = (int8_t *)r->buf[REF_REF_IDX0].p, *ri1 = (int8_t *)r->buf[REF_REF_IDX1].p;
     for (int k = 0; k < 3; k++) {
-      const int cw = P.width >> (k ? 1 : 0), ch = P.height >> (k ? 1 : 0), mg = HM_REF_MARGIN >> (k ? 1 : 0), st = cw + 2 * mg;
-      hipLaunchKernelGGL(hm355_ref_kernel, dim3((st + 63) / 64, ch + 2 * mg, 1), dim3(64, 1, 1), 0, c->stream, c->dP, slot, k, pl[k], pm, mv[0], mv[1], ri[0], ri[1]);
+      const int ch = P.height >> (k ? 1 : 0), mg = HM_REF_MARGIN >> (k ? 1 : 0), st = r->dev.stride[k];
+      hipLaunchKernelGGL(hm355_ref_kernel, dim3((st + 63) / 64, ch + 2 * mg, 1), dim3(64, 1, 1), 0, s, dP, slot, k, (Pel *)r->buf[REF_Y + k].p, pm, mv0, mv1, ri0, ri1);
     }
-    hipLaunchKernelGGL(hm355_ref_kernel, dim3((unsigned)((np + 63) / 64), 1, 1), dim3(64, 1, 1), 0, c->stream, c->dP, slot, 3, pl[0], pm, mv[0], mv[1], ri[0], ri[1]);
+    const size_t np = (size_t)c->numCtus * 256;
+    hipLaunchKernelGGL(hm355_ref_kernel, dim3((unsigned)((np + 63) / 64), 1, 1), dim3(64, 1, 1), 0, s, dP, slot, 3, (Pel *)r->buf[REF_Y].p, pm, mv0, mv1, ri0, ri1);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
   }
-  if (e != hipSuccess) { c->err = std::string("hm355_ref_from_slot: ") + hipGetErrorString(e); hm355_ref_release(c, r); return HM355_ERR_DEVICE; }
-  r->dev.predMode = pm; r->dev.mv[0] = mv[0]; r->dev.mv[1] = mv[1]; r->dev.refIdx[0] = ri[0]; r->dev.refIdx[1] = ri[1];
+  if (e != hipSuccess) { c->err = std::string("hm355_ref_from_slot: ") + hipGetErrorString(e); return HM355_ERR_DEVICE; }
   r->dev.poc = poc; r->dev.isLongTerm = 0;
   if (ref_poc) memcpy(r->dev.refPoc, ref_poc, sizeof(r->dev.refPoc));
   if (ref_lt) memcpy(r->dev.refLT, ref_lt, sizeof(r->dev.refLT));
   (void)num_ref;
-  *out = r;
+  *out = r.release();
   return HM355_OK;
 }
 
@@ -955,24 +986,21 @@ extern "C" int hm355_ref_from_slot(hm355_ctx *c, int slot, int32_t poc, int32_t 
 // pictures are all-gathered): header, the three border-extended planes, the compressed motion field.  buf may be host or device memory,
 // so a device buffer goes to RCCL as it is.
 struct RefBlobHdr { uint32_t magic, width, height, bitDepth; int32_t stride[3], poc, isLongTerm, refPoc[2][16], refLT[2][16]; double user[4]; };
-static size_t ref_plane_bytes(const hm355_ctx *c, int k)
-{ const int cw = c->hp.width >> (k ? 1 : 0), ch = c->hp.height >> (k ? 1 : 0), mg = HM_REF_MARGIN >> (k ? 1 : 0); return (size_t)(cw + 2 * mg) * (ch + 2 * mg) * sizeof(Pel); }
 extern "C" size_t hm355_ref_bytes(const hm355_ctx *c)
 {
   if (!c) return 0;
-  const size_t np = (size_t)c->numCtus * 256;
-  size_t n = (sizeof(RefBlobHdr) + 255) & ~(size_t)255;
-  for (int k = 0; k < 3; k++) n += (ref_plane_bytes(c, k) + 255) & ~(size_t)255;
-  return n + ((np + 255) & ~(size_t)255) + 2 * (((np * sizeof(MvD)) + 255) & ~(size_t)255) + 2 * ((np + 255) & ~(size_t)255);
+  size_t bytes[REF_NBUF]; ref_buf_bytes(c, bytes);
+  size_t n = align256(sizeof(RefBlobHdr));
+  for (int i = 0; i < REF_NBUF; i++) n += align256(bytes[i]);
+  return n;
 }
 static int ref_blob_copy(hm355_ctx *c, hm355_ref *r, uint8_t *p, int toBlob)
-{ // the buffers of r in the order hm355_ref_from_slot allocates them: planes Y, Cb, Cr, predMode, mv0, refIdx0, mv1, refIdx1
-  const size_t np = (size_t)c->numCtus * 256;
-  const size_t sizes[8] = { ref_plane_bytes(c, 0), ref_plane_bytes(c, 1), ref_plane_bytes(c, 2), np, np * sizeof(MvD), np, np * sizeof(MvD), np };
-  if (r->owned.size() != 8) return fail(c, HM355_ERR_ARG, "hm355_ref_export / import: not a device-resident reference picture");
-  for (int i = 0; i < 8; i++) {
-    HM_CHECK(c, toBlob ? hipMemcpy(p, r->owned[i], sizes[i], hipMemcpyDefault) : hipMemcpy(r->owned[i], p, sizes[i], hipMemcpyDefault));
-    p += (sizes[i] + 255) & ~(size_t)255;
+{ // the buffers of r in the order of RefBuf, each at a 256-byte boundary of the blob
+  size_t bytes[REF_NBUF]; ref_buf_bytes(c, bytes);
+  for (int i = 0; i < REF_NBUF; i++) if (!r->buf[i]) return fail(c, HM355_ERR_ARG, "hm355_ref_export / import: not a device-resident reference picture");
+  for (int i = 0; i < REF_NBUF; i++) {
+    HM_CHECK(c, toBlob ? hipMemcpy(p, r->buf[i], bytes[i], hipMemcpyDefault) : hipMemcpy(r->buf[i], p, bytes[i], hipMemcpyDefault));
+    p += align256(bytes[i]);
   }
   return HM355_OK;
 }
@@ -985,7 +1013,7 @@ extern "C" int hm355_ref_export(hm355_ctx *c, const hm355_ref *r, void *buf, con
   h.poc = r->dev.poc; h.isLongTerm = r->dev.isLongTerm; memcpy(h.refPoc, r->dev.refPoc, sizeof(h.refPoc)); memcpy(h.refLT, r->dev.refLT, sizeof(h.refLT));
   if (user) memcpy(h.user, user, sizeof(h.user));
   HM_CHECK(c, hipMemcpy(buf, &h, sizeof(h), hipMemcpyDefault));
-  return ref_blob_copy(c, (hm355_ref *)r, (uint8_t *)buf + ((sizeof(RefBlobHdr) + 255) & ~(size_t)255), 1);
+  return ref_blob_copy(c, (hm355_ref *)r, (uint8_t *)buf + align256(sizeof(RefBlobHdr)), 1);
 }
 extern "C" int hm355_ref_import(hm355_ctx *c, const void *buf, hm355_ref **out, double user[4])
 {
@@ -994,26 +1022,14 @@ extern "C" int hm355_ref_import(hm355_ctx *c, const void *buf, hm355_ref **out, 
   HM_CHECK(c, hipMemcpy(&h, buf, sizeof(h), hipMemcpyDefault));
   if (h.magic != 0x52464d48u || (int)h.width != c->hp.width || (int)h.height != c->hp.height || (int)h.bitDepth != c->hp.bitDepth)
     return fail(c, HM355_ERR_ARG, "hm355_ref_import: not a reference picture of this sequence");
-  const Params &P = c->hp; const size_t np = (size_t)c->numCtus * 256;
-  hm355_ref *r = new hm355_ref(); memset(&r->dev, 0, sizeof(r->dev));
-  const size_t sizes[8] = { ref_plane_bytes(c, 0), ref_plane_bytes(c, 1), ref_plane_bytes(c, 2), np, np * sizeof(MvD), np, np * sizeof(MvD), np };
-  for (int i = 0; i < 8; i++) {
-    void *d = NULL;
-    if (hipMalloc(&d, sizes[i]) != hipSuccess) { (void)hipGetLastError(); hm355_ref_release(c, r); return fail(c, HM355_ERR_NOMEM, "hm355_ref_import: out of device memory"); }
-    r->owned.push_back(d);
-  }
-  for (int k = 0; k < 3; k++) {
-    const int mg = HM_REF_MARGIN >> (k ? 1 : 0), st = (P.width >> (k ? 1 : 0)) + 2 * mg;
-    if (h.stride[k] != st) { hm355_ref_release(c, r); return fail(c, HM355_ERR_ARG, "hm355_ref_import: plane layout mismatch"); }
-    r->dev.plane[k] = (Pel *)r->owned[k] + (size_t)mg * st + mg; r->dev.stride[k] = st;
-  }
-  r->dev.predMode = (uint8_t *)r->owned[3]; r->dev.mv[0] = (MvD *)r->owned[4]; r->dev.refIdx[0] = (int8_t *)r->owned[5];
-  r->dev.mv[1] = (MvD *)r->owned[6]; r->dev.refIdx[1] = (int8_t *)r->owned[7];
+  std::unique_ptr<hm355_ref> r(new hm355_ref());
+  if (ref_alloc(c, r.get()) != hipSuccess) { (void)hipGetLastError(); return fail(c, HM355_ERR_NOMEM, "hm355_ref_import: out of device memory"); }
+  for (int k = 0; k < 3; k++) if (h.stride[k] != r->dev.stride[k]) return fail(c, HM355_ERR_ARG, "hm355_ref_import: plane layout mismatch");
   r->dev.poc = h.poc; r->dev.isLongTerm = h.isLongTerm; memcpy(r->dev.refPoc, h.refPoc, sizeof(h.refPoc)); memcpy(r->dev.refLT, h.refLT, sizeof(h.refLT));
   if (user) memcpy(user, h.user, sizeof(h.user));
-  const int rc = ref_blob_copy(c, r, (uint8_t *)buf + ((sizeof(RefBlobHdr) + 255) & ~(size_t)255), 0);
-  if (rc != HM355_OK) { hm355_ref_release(c, r); return rc; }
-  *out = r;
+  const int rc = ref_blob_copy(c, r.get(), (uint8_t *)buf + align256(sizeof(RefBlobHdr)), 0);
+  if (rc != HM355_OK) return rc;
+  *out = r.release();
   return HM355_OK;
 }
 
@@ -1028,27 +1044,22 @@ extern "C" int hm355_deblock_run(hm355_ctx *c, int n, const hm355_dbk_desc *desc
   for (int f = 0; f < n; f++) {
     if (descs[f].slice_type < 0 || descs[f].slice_type > 2 || descs[f].qp < 0 || descs[f].qp > 51) return fail(c, HM355_ERR_ARG, "bad deblocking parameters");
     if (descs[f].slice_type != 2 && !c->slots[f].imeta) return fail(c, HM355_ERR_ARG, "hm355_deblock_run: the slot holds no motion data (run hm355_compress_slices_inter first)");
-    fbs[f] = c->slots[f].fb; fbs[f].imeta = descs[f].slice_type != 2 ? c->slots[f].imeta : NULL;
+    fbs[f] = c->slots[f].fb; fbs[f].imeta = descs[f].slice_type != 2 ? c->slots[f].imeta.p : NULL;
     dps[f].sliceType = descs[f].slice_type; dps[f].qp = descs[f].qp; memcpy(dps[f].refPoc, descs[f].ref_poc, sizeof(dps[f].refPoc));
   }
-  if (!c->dDbk) HM_CHECK(c, hipMalloc((void **)&c->dDbk, sizeof(DbkParams) * c->slots.size()));
-  HM_CHECK(c, hipMemcpyAsync(c->dFrames, fbs.data(), sizeof(FrameBuf) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipMemcpyAsync(c->dDbk, dps.data(), sizeof(DbkParams) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  HM_CHECK(c, hipEventRecord(c->ev0, c->stream));
+  const int rc = stage_slots(c, fbs, c->dDbk, dps);
+  if (rc != HM355_OK) return rc;
   const int w = P.width, h = P.height;
   const dim3 blk(64, 1, 1);
-  // vertical edges (luma, chroma), then horizontal edges: the stream orders the two directions
-  hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 8 + 63) / 64, h / 4, n), blk, 0, c->stream, c->dP, c->dDbk, 0);
-  hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 16 + 63) / 64, h / 4, n), blk, 0, c->stream, c->dP, c->dDbk, 1);
-  hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 4 + 63) / 64, (h / 8 > 1 ? h / 8 : 1), n), blk, 0, c->stream, c->dP, c->dDbk, 2);
-  hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 4 + 63) / 64, (h / 16 > 1 ? h / 16 : 1), n), blk, 0, c->stream, c->dP, c->dDbk, 3);
-  HM_CHECK(c, hipGetLastError());
-  HM_CHECK(c, hipEventRecord(c->ev1, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  float ms = 0; HM_CHECK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->lastKernelMs = ms; c->lastLaunches = 4;
-  return HM355_OK;
+  const Params *dP = c->lane[0].dP; const DbkParams *dDbk = c->dDbk;
+  return timed_launches(c, 4, [&](hipStream_t s) {
+    // vertical edges (luma, chroma), then horizontal edges: the stream orders the two directions
+    hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 8 + 63) / 64, h / 4, n), blk, 0, s, dP, dDbk, 0);
+    hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 16 + 63) / 64, h / 4, n), blk, 0, s, dP, dDbk, 1);
+    hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 4 + 63) / 64, (h / 8 > 1 ? h / 8 : 1), n), blk, 0, s, dP, dDbk, 2);
+    hipLaunchKernelGGL(hm355_dbk_kernel, dim3((w / 4 + 63) / 64, (h / 16 > 1 ? h / 16 : 1), n), blk, 0, s, dP, dDbk, 3);
+    return hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1064,33 +1075,29 @@ extern "C" int hm355_sao_run(hm355_ctx *c, int n, hm355_sao_desc *descs)
     if (d.qp < 0 || d.qp > 51 || d.cabac_init_type < 0 || d.cabac_init_type > 2 || d.depth < 0 || d.depth > 7 || !(d.lambda > 0) || !(d.chroma_weight > 0))
       return fail(c, HM355_ERR_ARG, "bad SAO parameters");
     Slot &sl = c->slots[f];
-    for (int k = 0; k < 3; k++) if (!sl.saoSrc[k]) HM_CHECK(c, hipMalloc((void **)&sl.saoSrc[k], (size_t)P.stride[k] * P.hCtu * (k ? 32 : 64) * sizeof(Pel)));
-    if (!sl.saoStat) HM_CHECK(c, hipMalloc((void **)&sl.saoStat, sizeof(SaoStat) * 3 * c->numCtus));
-    if (!sl.saoCand) HM_CHECK(c, hipMalloc((void **)&sl.saoCand, sizeof(SaoCand) * 3 * SAO_NUM_TYPES * c->numCtus));
-    if (!sl.saoCoded) HM_CHECK(c, hipMalloc((void **)&sl.saoCoded, sizeof(SaoBlk) * c->numCtus));
-    if (!sl.saoRecon) HM_CHECK(c, hipMalloc((void **)&sl.saoRecon, sizeof(SaoBlk) * c->numCtus));
+    for (int k = 0; k < 3; k++) HM_CHECK(c, sl.saoSrc[k].ensure((size_t)P.stride[k] * P.hCtu * (k ? 32 : 64)));
+    HM_CHECK(c, sl.saoStat.ensure(3 * (size_t)c->numCtus));
+    HM_CHECK(c, sl.saoCand.ensure(3 * SAO_NUM_TYPES * (size_t)c->numCtus));
+    HM_CHECK(c, sl.saoCoded.ensure(c->numCtus));
+    HM_CHECK(c, sl.saoRecon.ensure(c->numCtus));
     fbs[f] = sl.fb;
     SaoParams &sp = sps[f]; memset(&sp, 0, sizeof(sp));
     sp.qp = d.qp; sp.cabacInitType = d.cabac_init_type; sp.depth = d.depth;
     sp.lambda[0] = d.lambda; sp.lambda[1] = sp.lambda[2] = d.lambda / d.chroma_weight;
     for (int k = 0; k < 3; k++) { sp.disabledPrev[k] = d.depth > 0 ? d.disabled_rate[k][d.depth - 1] : 0.0; sp.src[k] = sl.saoSrc[k]; }
     sp.stat = sl.saoStat; sp.cand = sl.saoCand; sp.coded = sl.saoCoded; sp.recon = sl.saoRecon;
-    for (int k = 0; k < 3; k++)
-      HM_CHECK(c, hipMemcpyAsync(sl.saoSrc[k], sl.fb.rec[k], (size_t)P.stride[k] * P.hCtu * (k ? 32 : 64) * sizeof(Pel), hipMemcpyDeviceToDevice, c->stream));
+    for (int k = 0; k < 3; k++) HM_CHECK(c, hipMemcpyAsync(sl.saoSrc[k], sl.fb.rec[k], sizeof(Pel) * sl.saoSrc[k].n, hipMemcpyDeviceToDevice, c->lane[0].stream));
   }
-  if (!c->dSao) HM_CHECK(c, hipMalloc((void **)&c->dSao, sizeof(SaoParams) * c->slots.size()));
-  HM_CHECK(c, hipMemcpyAsync(c->dFrames, fbs.data(), sizeof(FrameBuf) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipMemcpyAsync(c->dSao, sps.data(), sizeof(SaoParams) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  HM_CHECK(c, hipEventRecord(c->ev0, c->stream));
-  hipLaunchKernelGGL(hm355_sao_stats_kernel, dim3(c->numCtus, 3, n), dim3(64, 1, 1), 0, c->stream, c->dP, c->dSao);
-  hipLaunchKernelGGL(hm355_sao_decide_kernel, dim3(n, 1, 1), dim3(64, 1, 1), 0, c->stream, c->dP, c->dSao);
-  hipLaunchKernelGGL(hm355_sao_apply_kernel, dim3((P.width + 63) / 64, P.height, 3 * n), dim3(64, 1, 1), 0, c->stream, c->dP, c->dSao);
-  HM_CHECK(c, hipGetLastError());
-  HM_CHECK(c, hipEventRecord(c->ev1, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  float ms = 0; HM_CHECK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->lastKernelMs = ms; c->lastLaunches = 3;
+  int rc = stage_slots(c, fbs, c->dSao, sps);
+  if (rc != HM355_OK) return rc;
+  const Params *dP = c->lane[0].dP; SaoParams *dSao = c->dSao;
+  rc = timed_launches(c, 3, [&](hipStream_t s) {
+    hipLaunchKernelGGL(hm355_sao_stats_kernel, dim3(c->numCtus, 3, n), dim3(64, 1, 1), 0, s, dP, dSao);
+    hipLaunchKernelGGL(hm355_sao_decide_kernel, dim3(n, 1, 1), dim3(64, 1, 1), 0, s, dP, dSao);
+    hipLaunchKernelGGL(hm355_sao_apply_kernel, dim3((P.width + 63) / 64, P.height, 3 * n), dim3(64, 1, 1), 0, s, dP, dSao);
+    return hipGetLastError();
+  });
+  if (rc != HM355_OK) return rc;
   HM_CHECK(c, hipMemcpy(sps.data(), c->dSao, sizeof(SaoParams) * n, hipMemcpyDeviceToHost));
   for (int f = 0; f < n; f++) {
     hm355_sao_desc &d = descs[f];
@@ -1110,30 +1117,19 @@ extern "C" int hm355_deblock(hm355_ctx *c, const hm355_dbk_desc *desc, const hm3
 {
   if (!c || !desc || !ctus || !rec) return HM355_ERR_ARG;
   if (desc->slice_type != 2 && !ictus) return fail(c, HM355_ERR_ARG, "hm355_deblock: inter slices need the motion data");
-  const Params &P = c->hp; Slot &sl = c->slots[0]; FrameBuf &fb = sl.fb;
-  for (int k = 0; k < 3; k++) {
-    if (!rec->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
-    const int w = P.width >> (k ? 1 : 0), h = P.height >> (k ? 1 : 0);
-    HM_CHECK(c, hipMemcpy2D(fb.rec[k], (size_t)P.stride[k] * sizeof(Pel), rec->plane[k], (size_t)w * 2, (size_t)w * 2, h, hipMemcpyHostToDevice));
-  }
+  Slot &sl = c->slots[0]; FrameBuf &fb = sl.fb;
+  for (int k = 0; k < 3; k++) if (!rec->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
+  HM_CHECK(c, copy_planes(c, fb.rec, rec->plane, hipMemcpyHostToDevice, false));
   std::vector<CtuMeta> meta(c->numCtus);
-  for (int a = 0; a < c->numCtus; a++) {
-    const hm355_ctu_out *o = ctus + a; CtuMeta *m = &meta[a];
-    memcpy(m->depth, o->depth, 256); memcpy(m->part, o->part_size, 256); memcpy(m->pred, o->pred_mode, 256);
-    memcpy(m->dirL, o->intra_dir_luma, 256); memcpy(m->dirC, o->intra_dir_chroma, 256); memcpy(m->tr, o->tr_idx, 256);
-    memcpy(m->cbf, o->cbf, 768); memcpy(m->ts, o->tskip, 768);
-  }
+  for (int a = 0; a < c->numCtus; a++) ctu_from_out(ctus[a], &meta[a], NULL);
   HM_CHECK(c, hipMemcpy(fb.meta, meta.data(), sizeof(CtuMeta) * c->numCtus, hipMemcpyHostToDevice));
   if (desc->slice_type != 2) {
-    if (!sl.imeta) HM_CHECK(c, hipMalloc((void **)&sl.imeta, sizeof(InterMeta) * c->numCtus));
+    HM_CHECK(c, sl.imeta.ensure(c->numCtus));
     HM_CHECK(c, hipMemcpy(sl.imeta, ictus, sizeof(InterMeta) * c->numCtus, hipMemcpyHostToDevice));
   }
   int rc = hm355_deblock_run(c, 1, desc);
   if (rc != HM355_OK) return rc;
-  for (int k = 0; k < 3; k++) {
-    const int w = P.width >> (k ? 1 : 0), h = P.height >> (k ? 1 : 0);
-    HM_CHECK(c, hipMemcpy2D(rec->plane[k], (size_t)w * 2, fb.rec[k], (size_t)P.stride[k] * sizeof(Pel), (size_t)w * 2, h, hipMemcpyDeviceToHost));
-  }
+  HM_CHECK(c, copy_planes(c, fb.rec, rec->plane, hipMemcpyDeviceToHost, false));
   return HM355_OK;
 }
 
@@ -1142,21 +1138,16 @@ extern "C" int hm355_deblock(hm355_ctx *c, const hm355_dbk_desc *desc, const hm3
 // ------------------------------------------------------------------------------------------------
 static int ingest_launch(hm355_ctx *c, int n, const std::vector<IngestParams> &ips, int output, int gridW, int gridH)
 {
-  if (!c->dIngest) HM_CHECK(c, hipMalloc((void **)&c->dIngest, sizeof(IngestParams) * c->slots.size()));
   std::vector<FrameBuf> fbs(n); for (int f = 0; f < n; f++) fbs[f] = c->slots[f].fb;
-  HM_CHECK(c, hipMemcpyAsync(c->dFrames, fbs.data(), sizeof(FrameBuf) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipMemcpyAsync(c->dIngest, ips.data(), sizeof(IngestParams) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  HM_CHECK(c, hipEventRecord(c->ev0, c->stream));
+  const int rc = stage_slots(c, fbs, c->dIngest, ips);
+  if (rc != HM355_OK) return rc;
   const dim3 grid(((unsigned)((gridW + 7) / 8) * (unsigned)gridH + HM_INGEST_BLOCK - 1) / HM_INGEST_BLOCK, 1, 3 * n);   // sized for the luma plane
-  if (output) hipLaunchKernelGGL(hm355_output_kernel, grid, dim3(HM_INGEST_BLOCK), 0, c->stream, c->dP, c->dIngest);
-  else hipLaunchKernelGGL(hm355_ingest_kernel, grid, dim3(HM_INGEST_BLOCK), 0, c->stream, c->dP, c->dIngest);
-  HM_CHECK(c, hipGetLastError());
-  HM_CHECK(c, hipEventRecord(c->ev1, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  float ms = 0; HM_CHECK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->lastKernelMs = ms; c->lastLaunches = 1;
-  return HM355_OK;
+  const Params *dP = c->lane[0].dP; const IngestParams *dIngest = c->dIngest;
+  return timed_launches(c, 1, [&](hipStream_t s) {
+    if (output) hipLaunchKernelGGL(hm355_output_kernel, grid, dim3(HM_INGEST_BLOCK), 0, s, dP, dIngest);
+    else hipLaunchKernelGGL(hm355_ingest_kernel, grid, dim3(HM_INGEST_BLOCK), 0, s, dP, dIngest);
+    return hipGetLastError();
+  });
 }
 
 extern "C" int hm355_upload_file_frames(hm355_ctx *c, int n, const void *const *frames, int file_width, int file_height, int file_bit_depth)
@@ -1170,8 +1161,8 @@ extern "C" int hm355_upload_file_frames(hm355_ctx *c, int n, const void *const *
   for (int f = 0; f < n; f++) {
     if (!frames[f]) return fail(c, HM355_ERR_ARG, "null frame");
     Slot &sl = c->slots[f];
-    if (!sl.rawIn) HM_CHECK(c, hipMalloc((void **)&sl.rawIn, maxBytes));
-    HM_CHECK(c, hipMemcpyAsync(sl.rawIn, frames[f], bytes, hipMemcpyHostToDevice, c->stream));
+    HM_CHECK(c, sl.rawIn.ensure(maxBytes));
+    HM_CHECK(c, hipMemcpyAsync(sl.rawIn, frames[f], bytes, hipMemcpyHostToDevice, c->lane[0].stream));
     ips[f].src = sl.rawIn; ips[f].dst = NULL; ips[f].fileW = file_width; ips[f].fileH = file_height; ips[f].fileBitDepth = file_bit_depth; ips[f].fromOrg = 0;
   }
   return ingest_launch(c, n, ips, 0, P.width, P.height);
@@ -1180,12 +1171,8 @@ extern "C" int hm355_upload_file_frames(hm355_ctx *c, int n, const void *const *
 extern "C" int hm355_download_org(hm355_ctx *c, int slot, hm355_planes *org)
 {
   if (!c || !org || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
-  const Params &P = c->hp; FrameBuf &fb = c->slots[slot].fb;
-  for (int k = 0; k < 3; k++) {
-    if (!org->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
-    const int w = P.width >> (k ? 1 : 0), h = P.height >> (k ? 1 : 0);
-    HM_CHECK(c, hipMemcpy2D(org->plane[k], (size_t)w * 2, fb.org[k], (size_t)P.stride[k] * sizeof(Pel), (size_t)w * 2, h, hipMemcpyDeviceToHost));
-  }
+  for (int k = 0; k < 3; k++) if (!org->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
+  HM_CHECK(c, copy_planes(c, c->slots[slot].fb.org, org->plane, hipMemcpyDeviceToHost, false));
   return HM355_OK;
 }
 
@@ -1201,7 +1188,7 @@ extern "C" int hm355_download_file_frames(hm355_ctx *c, int n, void *const *fram
   for (int f = 0; f < n; f++) {
     if (!frames[f]) return fail(c, HM355_ERR_ARG, "null frame");
     Slot &sl = c->slots[f];
-    if (!sl.rawOut) HM_CHECK(c, hipMalloc((void **)&sl.rawOut, maxBytes));
+    HM_CHECK(c, sl.rawOut.ensure(maxBytes));
     ips[f].src = NULL; ips[f].dst = sl.rawOut; ips[f].fileW = fw; ips[f].fileH = fh; ips[f].fileBitDepth = file_bit_depth; ips[f].fromOrg = source;
   }
   int rc = ingest_launch(c, n, ips, 1, fw, fh);
@@ -1218,11 +1205,11 @@ extern "C" int hm355_num_substreams(const hm355_ctx *c) { return c ? (c->hp.wpp 
 extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *descs)
 {
   if (!c || !descs || n < 1 || n > (int)c->slots.size()) return HM355_ERR_ARG;
-  const Params &P = c->hp;
+  const Params &P = c->hp; Lane &L0 = c->lane[0];
   const int numSub = P.wpp ? P.hCtu : 1;
   const size_t rawBytes = (size_t)c->numCtus * HM_BITS_CAP_PER_CTU;
   std::vector<FrameBuf> fbs(n); std::vector<BitsParams> bps(n);
-  c->epoch++; if (c->epoch == 0) c->epoch = 1;          // 0 is what a fresh flag array holds
+  next_epoch(c);
   for (int f = 0; f < n; f++) {
     hm355_bits_desc &d = descs[f];
     if (d.slice_type < 0 || d.slice_type > 2 || d.qp < 0 || d.qp > 51 || !d.out || !d.sub_sizes) return fail(c, HM355_ERR_ARG, "bad bitstream pass parameters");
@@ -1233,14 +1220,12 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
           d.max_merge_cand < 1 || d.max_merge_cand > 5) return fail(c, HM355_ERR_ARG, "bad inter slice header values");
     }
     if ((d.sao_enabled[0] || d.sao_enabled[1]) && !sl.saoCoded) return fail(c, HM355_ERR_ARG, "hm355_encode_slices_run: the slot holds no SAO parameters (run hm355_sao_run first)");
-    if (!sl.bitsRaw) HM_CHECK(c, hipMalloc((void **)&sl.bitsRaw, rawBytes));
-    if (!sl.bitsPacked) HM_CHECK(c, hipMalloc((void **)&sl.bitsPacked, rawBytes));
-    if (!sl.bitsSizes) HM_CHECK(c, hipMalloc((void **)&sl.bitsSizes, sizeof(uint32_t) * P.hCtu));
-    if (!sl.bitsSync) HM_CHECK(c, hipMalloc((void **)&sl.bitsSync, sizeof(CabacW) * P.hCtu));
-    if (!sl.bitsFlag) { HM_CHECK(c, hipMalloc((void **)&sl.bitsFlag, sizeof(uint32_t) * P.hCtu)); HM_CHECK(c, hipMemset(sl.bitsFlag, 0, sizeof(uint32_t) * P.hCtu)); }
+    HM_CHECK(c, sl.bitsRaw.ensure(rawBytes)); HM_CHECK(c, sl.bitsPacked.ensure(rawBytes));
+    HM_CHECK(c, sl.bitsSizes.ensure(P.hCtu)); HM_CHECK(c, sl.bitsSync.ensure(P.hCtu));
+    HM_CHECK(c, sl.bitsFlag.ensure(P.hCtu, true));
     fbs[f] = sl.fb; fbs[f].imeta = NULL; fbs[f].ip = NULL;
     if (d.slice_type != 2) {
-      if (!sl.bitsIp) HM_CHECK(c, hipMalloc((void **)&sl.bitsIp, sizeof(InterPic)));
+      HM_CHECK(c, sl.bitsIp.ensure(1));
       std::vector<InterPic> ipv(1); InterPic &ip = ipv[0];   // only the slice header values the PU syntax reads
       memset(&ip, 0, sizeof(ip));
       ip.sliceType = d.slice_type; ip.numRefIdx[0] = d.num_ref_idx[0]; ip.numRefIdx[1] = d.slice_type == 0 ? d.num_ref_idx[1] : 0;
@@ -1251,32 +1236,31 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
     BitsParams &bp = bps[f]; memset(&bp, 0, sizeof(bp));
     bp.sliceType = d.slice_type; bp.qp = d.qp; bp.cabacInitType = d.cabac_init_type;
     bp.saoEnabled[0] = d.sao_enabled[0]; bp.saoEnabled[1] = bp.saoEnabled[2] = d.sao_enabled[1];
-    bp.sao = (d.sao_enabled[0] || d.sao_enabled[1]) ? (const int32_t *)sl.saoCoded : NULL;
+    bp.sao = (d.sao_enabled[0] || d.sao_enabled[1]) ? (const int32_t *)sl.saoCoded.p : NULL;
     bp.raw = sl.bitsRaw; bp.capPerCtu = HM_BITS_CAP_PER_CTU; bp.packed = sl.bitsPacked; bp.subSizes = sl.bitsSizes;
-    bp.sync = sl.bitsSync; bp.syncFlag = sl.bitsFlag; bp.sched = c->dSched + 8; bp.epoch = c->epoch; bp.nextInitType = d.slice_type;
-    HM_CHECK(c, hipMemsetAsync(sl.bitsSizes, 0, sizeof(uint32_t) * P.hCtu, c->stream));     // a substream nobody coded (abandoned launch) has length 0
+    bp.sync = sl.bitsSync; bp.syncFlag = sl.bitsFlag; bp.sched = L0.dSched + 8; bp.epoch = c->epoch; bp.nextInitType = d.slice_type;
+    HM_CHECK(c, hipMemsetAsync(sl.bitsSizes, 0, sizeof(uint32_t) * P.hCtu, L0.stream));     // a substream nobody coded (abandoned launch) has length 0
   }
-  if (!c->dBits) HM_CHECK(c, hipMalloc((void **)&c->dBits, sizeof(BitsParams) * c->slots.size()));
-  HM_CHECK(c, hipMemcpyAsync(c->dFrames, fbs.data(), sizeof(FrameBuf) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipMemcpyAsync(c->dBits, bps.data(), sizeof(BitsParams) * n, hipMemcpyHostToDevice, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  HM_CHECK(c, hipEventRecord(c->ev0, c->stream));
+  int rc = stage_slots(c, fbs, c->dBits, bps);
+  if (rc != HM355_OK) return rc;
   // persistent grid, items handed out by ticket in dependency order (hm355_bits_kernel): any grid size drains, so the only bound is the number
   // of per-workgroup scratch areas
-  HM_CHECK(c, hipMemsetAsync(c->dSched + 8, 0, 8, c->stream));          // ticket = 0, abort = 0 for this launch
+  unsigned int *bsched = L0.dSched + 8;
   const int total = numSub * n;
-  const int grid = total < (int)c->wsCount ? total : (int)c->wsCount;
-  hipLaunchKernelGGL(hm355_bits_kernel, dim3(grid), dim3(64), 0, c->stream, c->dP, c->dBits, n, c->dSched + 8);
-  hipLaunchKernelGGL(hm355_bits_pack_kernel, dim3(numSub, n), dim3(64), 0, c->stream, c->dP, c->dBits, (const unsigned int *)(c->dSched + 8));
-  HM_CHECK(c, hipGetLastError());
-  HM_CHECK(c, hipEventRecord(c->ev1, c->stream));
-  HM_CHECK(c, hipStreamSynchronize(c->stream));
-  float ms = 0; HM_CHECK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->lastKernelMs = ms; c->lastLaunches = 2;
+  const int grid = total < (int)L0.dWs.n ? total : (int)L0.dWs.n;
+  const Params *dP = L0.dP; BitsParams *dBits = c->dBits;
+  rc = timed_launches(c, 2, [&](hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(bsched, 0, 8, s);          // ticket = 0, abort = 0 for this launch
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hm355_bits_kernel, dim3(grid), dim3(64), 0, s, dP, dBits, n, bsched);
+    hipLaunchKernelGGL(hm355_bits_pack_kernel, dim3(numSub, n), dim3(64), 0, s, dP, dBits, (const unsigned int *)bsched);
+    return hipGetLastError();
+  });
+  if (rc != HM355_OK) return rc;
   HM_CHECK(c, hipMemcpy(bps.data(), c->dBits, sizeof(BitsParams) * n, hipMemcpyDeviceToHost));
-  unsigned int bsched[2] = {0, 0};
-  HM_CHECK(c, hipMemcpy(bsched, c->dSched + 8, sizeof(bsched), hipMemcpyDeviceToHost));
-  if (bsched[1]) return fail(c, HM355_ERR_DEVICE, "bitstream pass: a WPP hand-off wait was abandoned");
+  unsigned int bs[2] = {0, 0};
+  HM_CHECK(c, hipMemcpy(bs, bsched, sizeof(bs), hipMemcpyDeviceToHost));
+  if (bs[1]) return fail(c, HM355_ERR_DEVICE, "bitstream pass: a WPP hand-off wait was abandoned");
   for (int f = 0; f < n; f++) {
     hm355_bits_desc &d = descs[f]; Slot &sl = c->slots[f];
     if (bps[f].overflow) return fail(c, HM355_ERR_DEVICE, "bitstream pass: a substream outgrew its buffer");
@@ -1297,22 +1281,15 @@ extern "C" int hm355_encode_slice(hm355_ctx *c, hm355_bits_desc *desc, const hm3
   if ((desc->sao_enabled[0] || desc->sao_enabled[1]) && !sao) return fail(c, HM355_ERR_ARG, "hm355_encode_slice: SAO enabled without parameters");
   Slot &sl = c->slots[0]; FrameBuf &fb = sl.fb;
   std::vector<CtuMeta> meta(c->numCtus); std::vector<TCoeff> coef((size_t)c->numCtus * HM_COEF_CTU);
-  for (int a = 0; a < c->numCtus; a++) {
-    const hm355_ctu_out *o = ctus + a; CtuMeta *m = &meta[a];
-    memcpy(m->depth, o->depth, 256); memcpy(m->part, o->part_size, 256); memcpy(m->pred, o->pred_mode, 256);
-    memcpy(m->dirL, o->intra_dir_luma, 256); memcpy(m->dirC, o->intra_dir_chroma, 256); memcpy(m->tr, o->tr_idx, 256);
-    memcpy(m->cbf, o->cbf, 768); memcpy(m->ts, o->tskip, 768);
-    memcpy(&coef[(size_t)a * HM_COEF_CTU], o->coeff_y, 4096 * 4); memcpy(&coef[(size_t)a * HM_COEF_CTU + 4096], o->coeff_cb, 1024 * 4);
-    memcpy(&coef[(size_t)a * HM_COEF_CTU + 5120], o->coeff_cr, 1024 * 4);
-  }
+  for (int a = 0; a < c->numCtus; a++) ctu_from_out(ctus[a], &meta[a], &coef[(size_t)a * HM_COEF_CTU]);
   HM_CHECK(c, hipMemcpy(fb.meta, meta.data(), sizeof(CtuMeta) * c->numCtus, hipMemcpyHostToDevice));
   HM_CHECK(c, hipMemcpy(fb.coef, coef.data(), sizeof(TCoeff) * coef.size(), hipMemcpyHostToDevice));
   if (desc->slice_type != 2) {
-    if (!sl.imeta) HM_CHECK(c, hipMalloc((void **)&sl.imeta, sizeof(InterMeta) * c->numCtus));
+    HM_CHECK(c, sl.imeta.ensure(c->numCtus));
     HM_CHECK(c, hipMemcpy(sl.imeta, ictus, sizeof(InterMeta) * c->numCtus, hipMemcpyHostToDevice));
   }
   if (sao) {
-    if (!sl.saoCoded) HM_CHECK(c, hipMalloc((void **)&sl.saoCoded, sizeof(SaoBlk) * c->numCtus));
+    HM_CHECK(c, sl.saoCoded.ensure(c->numCtus));
     HM_CHECK(c, hipMemcpy(sl.saoCoded, sao, sizeof(SaoBlk) * c->numCtus, hipMemcpyHostToDevice));
   }
   return hm355_encode_slices_run(c, 1, desc);
@@ -1324,32 +1301,27 @@ extern "C" int hm355_encode_slice(hm355_ctx *c, hm355_bits_desc *desc, const hm3
 extern "C" int hm355_dist_batch(hm355_ctx *c, int kind, int n, int bit_depth, int count, const int16_t *org, const int16_t *cur, uint32_t *out)
 {
   if (!c || !org || !cur || !out || count < 1 || kind < 0 || kind > 3 || (n != 4 && n != 8 && n != 16 && n != 32 && n != 64) || (bit_depth != 8 && bit_depth != 10)) return HM355_ERR_ARG;
-  const size_t bytes = (size_t)count * n * n * sizeof(Pel);
-  Pel *dO = NULL, *dC = NULL; uint32_t *dOut = NULL;
-  int rc = HM355_OK;
-  if (hipMalloc((void **)&dO, bytes) != hipSuccess || hipMalloc((void **)&dC, bytes) != hipSuccess || hipMalloc((void **)&dOut, (size_t)count * 4) != hipSuccess) rc = HM355_ERR_NOMEM;
-  if (rc == HM355_OK && (hipMemcpy(dO, org, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dC, cur, bytes, hipMemcpyHostToDevice) != hipSuccess)) rc = HM355_ERR_DEVICE;
-  if (rc == HM355_OK) {
-    const int grid = count < 65536 ? count : 65536;
-    hipLaunchKernelGGL(hm355_dist_kernel, dim3(grid), dim3(64), 0, c->stream, kind, n, bit_depth, count, (const Pel *)dO, (const Pel *)dC, dOut);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, dOut, (size_t)count * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = HM355_ERR_DEVICE; c->err = "dist kernel failed"; }
-  }
-  if (dO) hipFree(dO); if (dC) hipFree(dC); if (dOut) hipFree(dOut);
-  return rc;
+  const size_t samples = (size_t)count * n * n, bytes = samples * sizeof(Pel);
+  const hipStream_t s = c->lane[0].stream;
+  DevBuf<Pel> dO, dC; DevBuf<uint32_t> dOut;
+  if (dO.alloc(samples) != hipSuccess || dC.alloc(samples) != hipSuccess || dOut.alloc(count) != hipSuccess) return HM355_ERR_NOMEM;
+  if (hipMemcpy(dO, org, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dC, cur, bytes, hipMemcpyHostToDevice) != hipSuccess) return HM355_ERR_DEVICE;
+  const int grid = count < 65536 ? count : 65536;
+  hipLaunchKernelGGL(hm355_dist_kernel, dim3(grid), dim3(64), 0, s, kind, n, bit_depth, count, (const Pel *)dO.p, (const Pel *)dC.p, dOut.p);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipMemcpy(out, dOut, (size_t)count * 4, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "dist kernel failed"; return HM355_ERR_DEVICE; }
+  return HM355_OK;
 }
 
 extern "C" int hm355_transform_batch(hm355_ctx *c, int inverse, int n, int bit_depth, int use_dst, int count, const int32_t *in, int32_t *out)
 {
   if (!c || !in || !out || count < 1 || (n != 4 && n != 8 && n != 16 && n != 32) || (bit_depth != 8 && bit_depth != 10) || (use_dst && n != 4)) return HM355_ERR_ARG;
-  const size_t bytes = (size_t)count * n * n * 4;
-  int32_t *dI = NULL, *dOut = NULL; int rc = HM355_OK;
-  if (hipMalloc((void **)&dI, bytes) != hipSuccess || hipMalloc((void **)&dOut, bytes) != hipSuccess) rc = HM355_ERR_NOMEM;
-  if (rc == HM355_OK && hipMemcpy(dI, in, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = HM355_ERR_DEVICE;
-  if (rc == HM355_OK) {
-    const int grid = count < 65536 ? count : 65536;
-    hipLaunchKernelGGL(hm355_transform_kernel, dim3(grid), dim3(64), 0, c->stream, inverse, n, bit_depth, use_dst, count, (const int32_t *)dI, dOut);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, dOut, bytes, hipMemcpyDeviceToHost) != hipSuccess) { rc = HM355_ERR_DEVICE; c->err = "transform kernel failed"; }
-  }
-  if (dI) hipFree(dI); if (dOut) hipFree(dOut);
-  return rc;
+  const size_t samples = (size_t)count * n * n, bytes = samples * 4;
+  const hipStream_t s = c->lane[0].stream;
+  DevBuf<int32_t> dI, dOut;
+  if (dI.alloc(samples) != hipSuccess || dOut.alloc(samples) != hipSuccess) return HM355_ERR_NOMEM;
+  if (hipMemcpy(dI, in, bytes, hipMemcpyHostToDevice) != hipSuccess) return HM355_ERR_DEVICE;
+  const int grid = count < 65536 ? count : 65536;
+  hipLaunchKernelGGL(hm355_transform_kernel, dim3(grid), dim3(64), 0, s, inverse, n, bit_depth, use_dst, count, (const int32_t *)dI.p, dOut.p);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess || hipMemcpy(out, dOut, bytes, hipMemcpyDeviceToHost) != hipSuccess) { c->err = "transform kernel failed"; return HM355_ERR_DEVICE; }
+  return HM355_OK;
 }
