@@ -241,7 +241,15 @@ struct Slot {           // one picture resident in HBM
   // cu_qp_delta (hm355_set_dqp): device state of the picture, allocated on first use; dqpOn: the next searches of the slot run with it
   DevBuf<DqpPic> dDqp; DevBuf<int8_t> dCtuQp; DevBuf<CtuDqp> dDqpOut; DevBuf<uint8_t> dRowFlag; int dqpOn = 0, dqpFlagIn = 0;
   std::vector<int8_t> ctuQp; std::vector<uint8_t> rowFlag; hm355_slice_desc lastSlice = {};
+  // LCU-level rate control (hm355_set_ctu_rc): the lambda of every CTU (0: the slice's), the device records built from it, the feedback of the search
+  std::vector<double> rcLambda; std::vector<CtuRc> rc; DevBuf<CtuRc> dRc; DevBuf<CtuRcOut> dRcOut;
+  // slice-resident search (hm355_slice_begin*, hm355_run_ctus, hm355_slice_end): the slice is open, CTUs searched so far, the first CTU of the last
+  // hm355_run_ctus (DqpPic::firstCtu); an inter slice keeps its slice-level parameters and the carried integer MVs until hm355_slice_end
+  // rcSearched: the CTUs ctusDone counts were searched with the slot armed (their feedback records are valid)
+  int sliceOpen = 0, ctusDone = 0, rcSearched = 0; int32_t firstCtu = 0; DevBuf<InterPic> dIp; DevBuf<MvD> dIntMv;
+  int motionSet = 0; uint32_t motionSad = 0, motionSse = 0;   // the open inter slice's m_uiLambdaMotionSAD / SSE (CTUs without a lambda of their own)
 };
+#define HM_QP_SLICE ((int8_t)-128)   /* Slot::ctuQp of a CTU that hm355_set_ctu_rc has not given a QP: the slice QP */
 #define HM_BITS_CAP_PER_CTU 16384u   /* bytes reserved per CTU in the raw substream buffers: above the raw size of a 10-bit 4:2:0 CTU (7.7 KB) */
 #define HM_MAX_LANES 4
 struct Lane {           // one launch of the search in flight: its own stream, scratch areas, work list and scheduler words (lane_init)
@@ -252,7 +260,7 @@ struct Lane {           // one launch of the search in flight: its own stream, s
   DevBuf<unsigned int> dSched; // [0] ticket, [1] abort, [2] CTUs published by the launch (the spin timeout watches it); lane 0: [8] ticket, [9] abort of the bitstream launch
   std::vector<WorkItem> items; std::vector<int> stepStart; std::vector<FrameBuf> fbs;
   long long key[5] = {}; int keyValid = 0, fewWaves = -1;   // fewWaves: the value dP holds (-1: dP not written yet)
-  int busy = 0, grid = 0, inFixup = 0;
+  int busy = 0, grid = 0, inFixup = 0, prepared = 0;   // prepared: the launch ran on slots an open slice prepared (hm355_run_ctus)
   DevBuf<Pel> dTeamWin; size_t teamCap = 0;   // team launches (hm355_team.h): the helpers' reconstruction windows, for teamCap teams
   ~Lane() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (stream) (void)hipStreamDestroy(stream); }
 };
@@ -275,6 +283,7 @@ struct hm355_ctx {
   DevBuf<SaoParams> dSao;      // [max_batch] SAO parameters / results of the pictures in the slots
   DevBuf<BitsParams> dBits;    // [max_batch] bitstream pass parameters / results
   DevBuf<IngestParams> dIngest; // [max_batch] ingest / output parameters
+  DevBuf<int32_t> dIntraCost;  // [numCtus] hm355_intra_cost
 };
 
 #define HM_CHECK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HM355_ERR_DEVICE; } } while (0)
@@ -403,20 +412,30 @@ extern "C" int hm355_upload(hm355_ctx *c, int slot, const hm355_planes *org)
   for (int k = 0; k < 3; k++) if (!org->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
   HM_CHECK(c, copy_planes(c, c->slots[slot].fb.org, org->plane, hipMemcpyHostToDevice, true));
   HM_CHECK(c, hipStreamSynchronize(c->lane[0].stream));
+  c->slots[slot].ctusDone = 0;      // a new picture: nothing of it is searched yet
   return HM355_OK;
 }
 
 // cu_qp_delta state of a slot for the search about to be launched (hm355_set_dqp armed it): the quantiser parameters of every QP the CTUs can
 // take (they depend on the slice's lambda), the CTUs' QPs, m_bEncodeDQP on entry, the per-row assumptions under WaveFrontSynchro
-static int dqp_prepare(hm355_ctx *c, int slot, const hm355_slice_desc *sd, hipStream_t stream)
+// and the LCU-level rate control's records (hm355_set_ctu_rc) -- for every CTU when the slot holds an open slice (`resident`), so that hm355_set_ctu_rc
+// then only replaces the records it changes
+static CtuRc slot_rc_record(const hm355_ctx *c, const Slot &sl, int qp, double lambda)   // lambda 0: the slice's (Slot::lastSlice)
+{
+  CtuRc r = hm355_ctu_rc_record(c->hp.bitDepth, qp, lambda > 0 ? lambda : sl.lastSlice.lambda, sl.lastSlice.chroma_weight);
+  if (!(lambda > 0) && sl.motionSet) { r.lambdaMotionSAD = sl.motionSad; r.lambdaMotionSSE = sl.motionSse; }
+  return r;
+}
+static int dqp_prepare(hm355_ctx *c, int slot, const hm355_slice_desc *sd, hipStream_t stream, int resident)
 {
   Slot &sl = c->slots[slot]; const Params &P = c->hp;
   sl.lastSlice = *sd;
   if (!sl.dqpOn) { sl.fb.dqp = NULL; return HM355_OK; }
   HM_CHECK(c, sl.dDqp.ensure(1)); HM_CHECK(c, sl.dCtuQp.ensure(c->numCtus));
-  HM_CHECK(c, sl.dDqpOut.ensure(c->numCtus)); HM_CHECK(c, sl.dRowFlag.ensure(P.hCtu));
+  HM_CHECK(c, sl.dDqpOut.ensure(c->numCtus)); HM_CHECK(c, sl.dRowFlag.ensure(P.hCtu)); HM_CHECK(c, sl.dRcOut.ensure(c->numCtus));
   DqpPic *hp = new DqpPic; memset(hp, 0, sizeof(*hp));
   hp->flagIn = sl.dqpFlagIn; hp->sliceQp = sd->qp; hp->ctuQp = sl.dCtuQp; hp->out = sl.dDqpOut; hp->rowFlag = sl.dRowFlag;
+  hp->rcOut = sl.dRcOut; hp->firstCtu = 0;
   for (int q = -12; q <= 51; q++) {
     FrameBuf t; memset(&t, 0, sizeof(t));
     hm355_fill_slice_params(&t, P.bitDepth, q, sd->lambda, sd->chroma_weight);
@@ -424,8 +443,18 @@ static int dqp_prepare(hm355_ctx *c, int slot, const hm355_slice_desc *sd, hipSt
     for (int k = 0; k < 2; k++) { e.qpPer[k] = t.qpPer[k]; e.qpRem[k] = t.qpRem[k]; e.rdFactor[k] = t.rdFactor[k]; for (int l = 0; l < 4; l++) e.errScale[k][l] = t.errScale[k][l]; }
   }
   std::vector<int8_t> q(c->numCtus, (int8_t)sd->qp);
-  if (!sl.ctuQp.empty()) q = sl.ctuQp;
+  if (!sl.ctuQp.empty()) for (int a = 0; a < c->numCtus; a++) if (sl.ctuQp[a] != HM_QP_SLICE) q[a] = sl.ctuQp[a];
+  int anyLambda = 0;
+  for (size_t a = 0; a < sl.rcLambda.size(); a++) anyLambda |= sl.rcLambda[a] > 0;
+  if (resident || anyLambda) {
+    if (sl.dRc.ensure(c->numCtus) != hipSuccess) { delete hp; c->err = "hm355: out of device memory for the rate control records"; return HM355_ERR_NOMEM; }
+    sl.rc.resize(c->numCtus);
+    for (int a = 0; a < c->numCtus; a++)
+      sl.rc[a] = slot_rc_record(c, sl, q[a], (size_t)a < sl.rcLambda.size() ? sl.rcLambda[a] : 0.0);
+    hp->rc = sl.dRc;
+  }
   hipError_t e1 = hipMemcpyAsync(sl.dDqp, hp, sizeof(DqpPic), hipMemcpyHostToDevice, stream);
+  if (e1 == hipSuccess && hp->rc) e1 = hipMemcpyAsync(sl.dRc, sl.rc.data(), sizeof(CtuRc) * c->numCtus, hipMemcpyHostToDevice, stream);
   if (e1 == hipSuccess) e1 = hipMemcpyAsync(sl.dCtuQp, q.data(), c->numCtus, hipMemcpyHostToDevice, stream);
   if (e1 == hipSuccess) e1 = hipMemcpyAsync(sl.dRowFlag, sl.rowFlag.data(), P.hCtu, hipMemcpyHostToDevice, stream);
   if (e1 == hipSuccess) e1 = hipStreamSynchronize(stream);
@@ -435,10 +464,11 @@ static int dqp_prepare(hm355_ctx *c, int slot, const hm355_slice_desc *sd, hipSt
   return HM355_OK;
 }
 
-// Enqueues the search over CTU rows [row0, row1] of the pictures in slots [slot0, slot0 + n) on lane l and returns; rows above row0 hold
-// finished (or imported) CTUs.  Launches of different lanes run concurrently (each on its own stream with its own scratch areas), so the
-// drain of one step overlaps the fill of the next; their slot ranges must not overlap.
-static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_desc *slices, int row0, int row1)
+// Enqueues the search over CTUs [ctu0, ctu1] (coding order) of the pictures in slots [slot0, slot0 + n) on lane l and returns; the CTUs before ctu0
+// are finished (or imported).  slices NULL: the slots were prepared by hm355_slice_begin* (slice parameters, cu_qp_delta state).  Launches of
+// different lanes run concurrently (each on its own stream with its own scratch areas), so the drain of one step overlaps the fill of the next;
+// their slot ranges must not overlap.
+static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_desc *slices, int ctu0, int ctu1)
 {
   const Params &P = c->hp;
   int rc = lane_init(c, l);
@@ -447,19 +477,21 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   if (L.busy) return fail(c, HM355_ERR_ARG, "hm355_run_begin: the lane still has a launch in flight (hm355_run_wait first)");
   L.fbs.resize(n);
   for (int f = 0; f < n; f++) {
-    if (slices[f].slice_type != 2) return fail(c, HM355_ERR_ARG, "only I slices are supported");
-    if (slices[f].qp < 0 || slices[f].qp > 51 || !(slices[f].lambda > 0) || !(slices[f].chroma_weight > 0)) return fail(c, HM355_ERR_ARG, "bad slice parameters");
-    hm355_fill_slice_params(&c->slots[slot0 + f].fb, P.bitDepth, slices[f].qp, slices[f].lambda, slices[f].chroma_weight);
-    { const int rc2 = dqp_prepare(c, slot0 + f, slices + f, L.stream); if (rc2 != HM355_OK) return rc2; }
+    if (slices) {
+      if (slices[f].slice_type != 2) return fail(c, HM355_ERR_ARG, "only I slices are supported");
+      if (slices[f].qp < 0 || slices[f].qp > 51 || !(slices[f].lambda > 0) || !(slices[f].chroma_weight > 0)) return fail(c, HM355_ERR_ARG, "bad slice parameters");
+      hm355_fill_slice_params(&c->slots[slot0 + f].fb, P.bitDepth, slices[f].qp, slices[f].lambda, slices[f].chroma_weight);
+      { const int rc2 = dqp_prepare(c, slot0 + f, slices + f, L.stream, c->slots[slot0 + f].sliceOpen); if (rc2 != HM355_OK) return rc2; }
+    }
     L.fbs[f] = c->slots[slot0 + f].fb;
   }
   HM_CHECK(c, hipMemcpyAsync(c->dFrames + slot0, L.fbs.data(), sizeof(FrameBuf) * n, hipMemcpyHostToDevice, L.stream));
   int carry = 0;
   for (int f = 0; f < n; f++) carry |= c->slots[slot0 + f].fb.imeta != NULL && (P.height & 63) != 0;
-  const long long key[5] = {slot0, n, carry, row0, row1};      // the cached work list is reused only for the very same launch shape
+  const long long key[5] = {slot0, n, carry, ctu0, ctu1};      // the cached work list is reused only for the very same launch shape
   if (!L.keyValid || memcmp(key, L.key, sizeof(key)) != 0) {
     L.keyValid = 0;
-    hm355_build_schedule(P.wCtu, P.hCtu, P.wpp, n, L.items, L.stepStart, carry, slot0, row0, row1);
+    hm355_build_schedule(P.wCtu, P.hCtu, P.wpp, n, L.items, L.stepStart, carry, slot0, ctu0, ctu1);
     HM_CHECK(c, L.dItems.grow(L.items.size()));
     HM_CHECK(c, hipMemcpyAsync(L.dItems, L.items.data(), sizeof(WorkItem) * L.items.size(), hipMemcpyHostToDevice, L.stream));
     memcpy(L.key, key, sizeof(key)); L.keyValid = 1;
@@ -484,7 +516,8 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   if (useTeam) {
     const size_t total = L.items.size();
     // as many teams as CTUs can ever be ready at once (the wavefront's widest step), a few more so that a finished team finds the next ticket taken
-    size_t want = (size_t)maxItemsPerStep(P.wCtu, row1 - row0 + 1 < P.hCtu ? row1 - row0 + 1 : P.hCtu, P.wpp, n) + 2;
+    const int rows = ctu1 / P.wCtu - ctu0 / P.wCtu + 1;
+    size_t want = (size_t)maxItemsPerStep(P.wCtu, rows < P.hCtu ? rows : P.hCtu, P.wpp, n) + 2;
     if (want > total) want = total; if (want > 512) want = 512; if (want > wsCount / waves) want = wsCount / waves;
     if (want > L.teamCap) {   // the windows grow only after the lane's stream is idle; without them the launch runs without teams
       HM_CHECK(c, hipStreamSynchronize(L.stream));
@@ -503,8 +536,9 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   }
   next_epoch(c);
   HM_CHECK(c, hipMemsetAsync(L.dSched, 0, 32, L.stream));       // ticket = 0, abort = 0, published CTUs = 0 (+ the counters of diagnostic builds)
-  if (row0 > 0)    // the row above the band is complete: its CTUs count as published in this run
-    for (int f = 0; f < n; f++) HM_CHECK(c, hipMemsetD32Async((hipDeviceptr_t)(c->slots[slot0 + f].fb.done + (size_t)(row0 - 1) * P.wCtu), (int)c->epoch, P.wCtu, L.stream));
+  if (ctu0 > 0)    // the CTUs before the band are complete: they count as published in this run
+    for (int f = 0; f < n; f++) HM_CHECK(c, hipMemsetD32Async((hipDeviceptr_t)c->slots[slot0 + f].fb.done, (int)c->epoch, ctu0, L.stream));
+  L.prepared = slices == NULL;
   HM_CHECK(c, hipEventRecord(L.ev0, L.stream));
   const int total = (int)L.items.size();
   if (useTeam && teams > 0) {
@@ -534,22 +568,28 @@ static int run_wait(hm355_ctx *c, int l, double *kernelMs);
 // wavefront has not searched yet when that row starts.  The launch ran on an assumption per row (Slot::rowFlag, "clear" to begin with: a CTU with
 // any coded block leaves it clear); here the assumptions are checked against what the rows above actually left, and from the first row that was
 // started on a wrong one the picture is searched again with the corrected value -- rare, and then repeated for the rows below.
-static int dqp_verify_rows(hm355_ctx *c, int l, int slot0, int n)
+// Only rows whose first CTU the launch (CTUs [ctu0, ctu1]) searched with the CTU before it in the same launch are checked, and the search again covers
+// that row start .. ctu1: a CTU an earlier hm355_run_ctus finished (its feedback may be with the caller) is never searched again.
+static int dqp_verify_rows(hm355_ctx *c, int l, int slot0, int n, int ctu0, int ctu1, int prepared)
 {
   const Params &P = c->hp;
   if (!P.wpp || P.wCtu < 1) return HM355_OK;
   for (int f = 0; f < n; f++) {
     Slot &sl = c->slots[slot0 + f];
     if (!sl.dqpOn || !sl.fb.dqp) continue;
+    const int firstGuess = prepared ? (sl.firstCtu > ctu0 ? sl.firstCtu : ctu0) + 1 : 1;   // a row start at or after it used Slot::rowFlag
+    const int yLo = (firstGuess + P.wCtu - 1) / P.wCtu, yHi = ctu1 / P.wCtu;
     std::vector<CtuDqp> out(c->numCtus);
-    for (int y = 1; y < P.hCtu; y++) {
+    for (int y = yLo < 1 ? 1 : yLo; y <= yHi; y++) {
       HM_CHECK(c, hipMemcpy(out.data(), sl.dDqpOut, sizeof(CtuDqp) * c->numCtus, hipMemcpyDeviceToHost));
       int bad = -1;
-      for (int yy = y; yy < P.hCtu; yy++) if (sl.rowFlag[yy] != out[(size_t)yy * P.wCtu - 1].flagOut) { bad = yy; break; }
+      for (int yy = y; yy <= yHi; yy++) if (sl.rowFlag[yy] != out[(size_t)yy * P.wCtu - 1].flagOut) { bad = yy; break; }
       if (bad < 0) break;
       sl.rowFlag[bad] = out[(size_t)bad * P.wCtu - 1].flagOut;
       const hm355_slice_desc sd = sl.lastSlice;
-      int rc = run_begin(c, l, slot0 + f, 1, &sd, bad, P.hCtu - 1);
+      int rc = HM355_OK;
+      if (prepared) rc = hipMemcpyAsync(sl.dRowFlag.p + bad, &sl.rowFlag[bad], 1, hipMemcpyHostToDevice, c->lane[l].stream) == hipSuccess ? HM355_OK : fail(c, HM355_ERR_DEVICE, "row flag upload failed");
+      if (rc == HM355_OK) rc = run_begin(c, l, slot0 + f, 1, prepared ? NULL : &sd, bad * P.wCtu, ctu1);
       if (rc == HM355_OK) rc = run_wait(c, l, NULL);
       if (rc != HM355_OK) return rc;
       y = bad;
@@ -577,17 +617,22 @@ static int run_wait(hm355_ctx *c, int l, double *kernelMs)
   c->lastKernelMs = ms; c->lastLaunches = 1;
   if (kernelMs) *kernelMs = ms;
   if (L.keyValid && !L.inFixup) {
+    const int slot0 = (int)L.key[0], n = (int)L.key[1], ctu1 = (int)L.key[4];
     L.inFixup = 1;
-    const int rc = dqp_verify_rows(c, l, (int)L.key[0], (int)L.key[1]);
+    const int rc = dqp_verify_rows(c, l, slot0, n, (int)L.key[3], ctu1, L.prepared);
     L.inFixup = 0; L.keyValid = 0;          // the fix-up launches reused the lane's work list
     c->lastKernelMs = ms;
     if (rc != HM355_OK) return rc;
+    for (int f = 0; f < n; f++) {   // every CTU up to ctu1 is searched (hm355_run_ctus, hm355_ctu_rc_feedback)
+      Slot &sl = c->slots[slot0 + f];
+      sl.ctusDone = ctu1 + 1; sl.rcSearched = sl.fb.dqp != NULL;
+    }
   }
   return HM355_OK;
 }
 static int run_rows_impl(hm355_ctx *c, int slot0, int n, const hm355_slice_desc *slices, int row0, int row1)
 {
-  const int rc = run_begin(c, 0, slot0, n, slices, row0, row1);
+  const int rc = run_begin(c, 0, slot0, n, slices, row0 * c->hp.wCtu, (row1 + 1) * c->hp.wCtu - 1);
   return rc != HM355_OK ? rc : run_wait(c, 0, NULL);
 }
 
@@ -599,7 +644,7 @@ extern "C" int hm355_run_begin(hm355_ctx *c, int lane, int first_slot, int n, co
   for (int l = 0; l < HM_MAX_LANES; l++)
     if (l != lane && c->lane[l].busy && c->lane[l].keyValid && first_slot < (int)(c->lane[l].key[0] + c->lane[l].key[1]) && (int)c->lane[l].key[0] < first_slot + n)
       return fail(c, HM355_ERR_ARG, "hm355_run_begin: the slots overlap a launch in flight on another lane");
-  return run_begin(c, lane, first_slot, n, slices, 0, c->hp.hCtu - 1);
+  return run_begin(c, lane, first_slot, n, slices, 0, c->numCtus - 1);
 }
 extern "C" int hm355_set_lane_share(hm355_ctx *c, int launches_in_flight)
 {
@@ -645,6 +690,9 @@ extern "C" int hm355_set_dqp(hm355_ctx *c, int slot, const hm355_dqp_desc *d)
 {
   if (!c || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
   Slot &sl = c->slots[slot];
+  // the open slice's device state (DqpPic, records, row assumptions) was built from the arming at hm355_slice_begin*: it stays until hm355_slice_end
+  if (sl.sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_dqp: a slice is open on the slot (hm355_slice_end first)");
+  sl.rcLambda.clear();
   if (!d || !d->use_dqp) { sl.dqpOn = 0; sl.fb.dqp = NULL; sl.ctuQp.clear(); return HM355_OK; }
   const int lo = -6 * (c->hp.bitDepth - 8);
   sl.ctuQp.clear();
@@ -683,10 +731,188 @@ extern "C" int hm355_preanalyze(hm355_ctx *c, int slot, uint64_t *sums)
   return HM355_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// hm355_inter_slice_desc, shared by hm355_compress_slices_inter and hm355_slice_begin_inter: what both accept, and the slice-level parameters of the
+// search they build from it (InterPic; the reference pictures are filled in by each entry, then inter_pic_list1)
+// ------------------------------------------------------------------------------------------------
+static int inter_desc_check(hm355_ctx *c, const hm355_inter_slice_desc *sd, const char *who)
+{
+  const int isB = sd->base.slice_type == 0;
+  if (sd->base.slice_type != 1 && !isB) return fail(c, HM355_ERR_ARG, (std::string(who) + ": P (1) or B (0) slices").c_str());
+  if (sd->num_ref_idx[0] < 1 || sd->num_ref_idx[0] > 16 || (isB ? (sd->num_ref_idx[1] < 1 || sd->num_ref_idx[1] > 16) : sd->num_ref_idx[1] != 0) ||
+      sd->max_merge_cand < 1 || sd->max_merge_cand > 5 || (sd->cabac_init_type != 0 && sd->cabac_init_type != 1) ||
+      sd->col_ref_idx < 0 || sd->col_ref_idx >= sd->num_ref_idx[(isB && !sd->col_from_l0) ? 1 : 0])
+    return fail(c, HM355_ERR_ARG, "bad inter slice parameters");
+  return HM355_OK;
+}
+static void inter_pic_params(const hm355_inter_slice_desc *sd, InterPic *ip)
+{
+  memset(ip, 0, sizeof(*ip));
+  ip->sliceType = sd->base.slice_type; ip->poc = sd->poc; ip->numRefIdx[0] = sd->num_ref_idx[0]; ip->numRefIdx[1] = sd->num_ref_idx[1];
+  ip->colFromL0 = sd->col_from_l0; ip->colRefIdx = sd->col_ref_idx; ip->tmvp = sd->tmvp; ip->mvdL1Zero = sd->mvd_l1_zero;
+  ip->maxMergeCand = sd->max_merge_cand; ip->checkLDC = sd->check_ldc; ip->cabacInitType = sd->cabac_init_type;
+  ip->lambdaMotionSAD = sd->lambda_motion_sad; ip->lambdaMotionSSE = sd->lambda_motion_sse;
+}
+static void inter_pic_list1(const hm355_inter_slice_desc *sd, InterPic *ip)   // TComSlice::setList1IdxToList0Idx, once ref[][] is filled
+{
+  for (int i1 = 0; i1 < sd->num_ref_idx[1]; i1++) {
+    ip->list1ToList0[i1] = -1;
+    for (int i0 = 0; i0 < sd->num_ref_idx[0]; i0++) if (ip->ref[0][i0].poc == ip->ref[1][i1].poc) { ip->list1ToList0[i1] = i0; break; }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// LCU-level rate control (TEncSlice.cpp:766-887): a QP and a lambda per CTU, a slice searched CTU range by CTU range with the rate model's
+// feedback in between, and the intra cost the model needs before an I picture (TEncSlice::calCostSliceI)
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(hm355_ctu_rc) == sizeof(CtuRcOut), "hm355_ctu_rc mirrors CtuRcOut");
+// lambdas hm355_set_ctu_rc accepts: floor(65536 lambda) must fit the motion lambda's 32 bits and the sign-hiding factor (which divides by lambda)
+// its 64; the rate model's lambdas (TEncRateCtrl clips them to [0.1, 10000]) lie far inside
+#define HM_RC_LAMBDA_MIN 1e-4
+#define HM_RC_LAMBDA_MAX 65535.0
+// an open slice was begun on an armed slot, so its device state is complete (hm355_set_dqp is refused while it is open)
+static bool open_slice_armed(const hm355_ctx *c, const Slot &sl) { return sl.fb.dqp && sl.rc.size() == (size_t)c->numCtus && sl.dRc && sl.dRcOut; }
+extern "C" int hm355_set_ctu_rc(hm355_ctx *c, int slot, int first_ctu, int n, const int8_t *qp, const double *lambda)
+{
+  if (!c || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  Slot &sl = c->slots[slot];
+  if (!sl.dqpOn) return fail(c, HM355_ERR_ARG, "hm355_set_ctu_rc: the slot is not armed with cu_qp_delta (hm355_set_dqp with use_dqp 1 first)");
+  if (!qp || n < 1 || first_ctu < 0 || first_ctu + n > c->numCtus) return fail(c, HM355_ERR_ARG, "hm355_set_ctu_rc: bad CTU range (or no QPs)");
+  if (sl.sliceOpen && !open_slice_armed(c, sl)) return fail(c, HM355_ERR_ARG, "hm355_set_ctu_rc: the open slice was not begun on an armed slot");
+  if (sl.sliceOpen && first_ctu < sl.ctusDone) return fail(c, HM355_ERR_ARG, "hm355_set_ctu_rc: those CTUs of the open slice are searched already");
+  const int lo = -6 * (c->hp.bitDepth - 8);
+  for (int i = 0; i < n; i++) {
+    if (qp[i] < lo || qp[i] > 51) return fail(c, HM355_ERR_ARG, "hm355_set_ctu_rc: CTU QP outside [-QpBDOffset, 51]");
+    if (lambda && !(lambda[i] >= HM_RC_LAMBDA_MIN && lambda[i] <= HM_RC_LAMBDA_MAX)) return fail(c, HM355_ERR_ARG, "hm355_set_ctu_rc: a lambda must lie in [1e-4, 65535]");
+  }
+  if (sl.ctuQp.empty()) sl.ctuQp.assign(c->numCtus, HM_QP_SLICE);
+  if (sl.rcLambda.empty()) sl.rcLambda.assign(c->numCtus, 0.0);
+  for (int i = 0; i < n; i++) { sl.ctuQp[first_ctu + i] = qp[i]; sl.rcLambda[first_ctu + i] = lambda ? lambda[i] : 0.0; }
+  if (!sl.sliceOpen) return HM355_OK;        // the next whole-slice search builds the records (dqp_prepare)
+  // an open slice: only the changed records and QPs go to the device, on lane 0's stream (the next hm355_run_ctus is ordered behind them)
+  for (int i = 0; i < n; i++) sl.rc[first_ctu + i] = slot_rc_record(c, sl, qp[i], lambda ? lambda[i] : 0.0);
+  const hipStream_t s = c->lane[0].stream;
+  HM_CHECK(c, hipMemcpyAsync(sl.dRc.p + first_ctu, sl.rc.data() + first_ctu, sizeof(CtuRc) * n, hipMemcpyHostToDevice, s));
+  HM_CHECK(c, hipMemcpyAsync(sl.dCtuQp.p + first_ctu, sl.ctuQp.data() + first_ctu, (size_t)n, hipMemcpyHostToDevice, s));
+  return HM355_OK;
+}
+
+// the slot's slice parameters and cu_qp_delta state, once per slice (hm355_run_ctus then uploads only what changes)
+static int slice_open(hm355_ctx *c, int slot, const hm355_slice_desc *sd)
+{
+  Slot &sl = c->slots[slot];
+  hm355_fill_slice_params(&sl.fb, c->hp.bitDepth, sd->qp, sd->lambda, sd->chroma_weight);
+  const int rc = dqp_prepare(c, slot, sd, c->lane[0].stream, 1);
+  if (rc != HM355_OK) return rc;
+  sl.sliceOpen = 1; sl.ctusDone = 0; sl.firstCtu = 0;
+  return HM355_OK;
+}
+static int slice_begin_check(hm355_ctx *c, int slot, const hm355_slice_desc *sd)
+{
+  if (c->lane[0].busy) return fail(c, HM355_ERR_ARG, "hm355_slice_begin: lane 0 has a launch in flight (hm355_run_wait first)");
+  if (!c->slots[slot].dqpOn) return fail(c, HM355_ERR_ARG, "hm355_slice_begin: the slot is not armed with cu_qp_delta (hm355_set_dqp with use_dqp 1 first)");
+  if (sd->qp < 0 || sd->qp > 51 || !(sd->lambda > 0) || !(sd->chroma_weight > 0)) return fail(c, HM355_ERR_ARG, "bad slice parameters");
+  return HM355_OK;
+}
+extern "C" int hm355_slice_begin(hm355_ctx *c, int slot, const hm355_slice_desc *sd)
+{
+  if (!c || !sd || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  if (sd->slice_type != 2) return fail(c, HM355_ERR_ARG, "hm355_slice_begin: I slices (P / B: hm355_slice_begin_inter)");
+  const int rc = slice_begin_check(c, slot, sd);
+  if (rc != HM355_OK) return rc;
+  FrameBuf &fb = c->slots[slot].fb; fb.imeta = NULL; fb.ip = NULL; fb.intMv = NULL;
+  c->slots[slot].motionSet = 0;
+  return slice_open(c, slot, sd);
+}
+extern "C" int hm355_slice_begin_inter(hm355_ctx *c, int slot, const hm355_inter_slice_desc *sd)
+{
+  if (!c || !sd || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  int rc = inter_desc_check(c, sd, "hm355_slice_begin_inter");
+  if (rc != HM355_OK) return rc;
+  for (int l = 0; l < 2; l++) for (int i = 0; i < sd->num_ref_idx[l]; i++)
+    if (!sd->dev_ref[l][i])
+      return fail(c, HM355_ERR_ARG, "hm355_slice_begin_inter: device-resident references only (dev_ref, hm355_ref_from_slot); host hm355_ref_pic pictures go through hm355_compress_slices_inter");
+  rc = slice_begin_check(c, slot, &sd->base);
+  if (rc != HM355_OK) return rc;
+  InterPic hip; inter_pic_params(sd, &hip);
+  for (int l = 0; l < 2; l++) for (int i = 0; i < sd->num_ref_idx[l]; i++) hip.ref[l][i] = sd->dev_ref[l][i]->dev;
+  inter_pic_list1(sd, &hip);
+  Slot &sl = c->slots[slot];
+  HM_CHECK(c, sl.dIp.ensure(1)); HM_CHECK(c, sl.imeta.ensure(c->numCtus)); HM_CHECK(c, sl.dIntMv.ensure((size_t)c->numCtus * 32));
+  HM_CHECK(c, hipMemcpy(sl.dIp, &hip, sizeof(InterPic), hipMemcpyHostToDevice));
+  HM_CHECK(c, hipMemset(sl.imeta, 0, sizeof(InterMeta) * c->numCtus));
+  HM_CHECK(c, hipMemset(sl.dIntMv, 0, sizeof(MvD) * sl.dIntMv.n));
+  sl.fb.imeta = sl.imeta; sl.fb.ip = sl.dIp; sl.fb.intMv = sl.dIntMv;
+  sl.motionSet = 1; sl.motionSad = sd->lambda_motion_sad; sl.motionSse = sd->lambda_motion_sse;
+  return slice_open(c, slot, &sd->base);
+}
+extern "C" int hm355_run_ctus(hm355_ctx *c, int first_slot, int n, int first_ctu, int num_ctus)
+{
+  if (!c || n < 1 || first_slot < 0 || first_slot + n > (int)c->slots.size()) return HM355_ERR_ARG;
+  if (num_ctus < 1 || first_ctu < 0 || first_ctu + num_ctus > c->numCtus) return fail(c, HM355_ERR_ARG, "hm355_run_ctus: bad CTU range");
+  for (int f = 0; f < n; f++) {
+    const Slot &sl = c->slots[first_slot + f];
+    if (!sl.sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_run_ctus: no slice is open on the slot (hm355_slice_begin / hm355_slice_begin_inter first)");
+    if (!open_slice_armed(c, sl)) return fail(c, HM355_ERR_ARG, "hm355_run_ctus: the open slice was not begun on an armed slot");
+    if (sl.ctusDone != first_ctu)
+      return fail(c, HM355_ERR_ARG, "hm355_run_ctus: first_ctu must equal the number of CTUs already searched in the slice (coding order: no gap, no repeat)");
+  }
+  for (int f = 0; f < n; f++) {      // DqpPic::firstCtu: a row start of this range takes the real m_bEncodeDQP of the CTU an earlier call finished
+    Slot &sl = c->slots[first_slot + f];
+    if (!sl.fb.dqp) continue;
+    sl.firstCtu = first_ctu;
+    HM_CHECK(c, hipMemcpyAsync((uint8_t *)sl.dDqp.p + offsetof(DqpPic, firstCtu), &sl.firstCtu, sizeof(int32_t), hipMemcpyHostToDevice, c->lane[0].stream));
+  }
+  int rc = run_begin(c, 0, first_slot, n, NULL, first_ctu, first_ctu + num_ctus - 1);
+  if (rc == HM355_OK) rc = run_wait(c, 0, NULL);
+  return rc;                                // run_wait counted the CTUs as searched
+}
+extern "C" int hm355_ctu_rc_feedback(hm355_ctx *c, int slot, int first_ctu, int n, hm355_ctu_rc *out)
+{
+  if (!c || !out || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  const Slot &sl = c->slots[slot];
+  if (!sl.rcSearched || !sl.dRcOut) return fail(c, HM355_ERR_ARG, "hm355_ctu_rc_feedback: the slot's picture was not searched with cu_qp_delta");
+  if (n < 1 || first_ctu < 0 || first_ctu + n > sl.ctusDone) return fail(c, HM355_ERR_ARG, "hm355_ctu_rc_feedback: those CTUs are not searched yet");
+  HM_CHECK(c, hipMemcpy(out, sl.dRcOut.p + first_ctu, sizeof(CtuRcOut) * n, hipMemcpyDeviceToHost));
+  return HM355_OK;
+}
+extern "C" int hm355_download_inter(hm355_ctx *c, int slot, hm355_ctu_inter_out *ictus)
+{
+  if (!c || !ictus || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  if (!c->slots[slot].imeta) return fail(c, HM355_ERR_ARG, "hm355_download_inter: the slot holds no motion data");
+  HM_CHECK(c, hipMemcpy(ictus, c->slots[slot].imeta, sizeof(InterMeta) * c->numCtus, hipMemcpyDeviceToHost));
+  return HM355_OK;
+}
+extern "C" int hm355_slice_end(hm355_ctx *c, int slot)
+{
+  if (!c || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  Slot &sl = c->slots[slot];
+  if (!sl.sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_slice_end: no slice is open on the slot");
+  // the slot as hm355_compress_slices_inter leaves it: the motion arrays stay in Slot::imeta for the loop filter, the bitstream pass and
+  // hm355_ref_from_slot; the searches that follow start from the slot's slice parameters again
+  sl.sliceOpen = 0; sl.fb.imeta = NULL; sl.fb.ip = NULL; sl.fb.intMv = NULL;
+  return HM355_OK;
+}
+extern "C" int hm355_intra_cost(hm355_ctx *c, int slot, int32_t *cost)
+{
+  if (!c || !cost || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  HM_CHECK(c, hipMemcpy(c->dFrames + slot, &c->slots[slot].fb, sizeof(FrameBuf), hipMemcpyHostToDevice));
+  HM_CHECK(c, c->dIntraCost.ensure(c->numCtus));
+  const Params *dP = c->lane[0].dP; int32_t *d = c->dIntraCost;
+  const int rc = timed_launches(c, 1, [&](hipStream_t s) {
+    hipLaunchKernelGGL(hm355_intra_cost_kernel, dim3(c->numCtus), dim3(64), 0, s, dP, slot, d);
+    return hipGetLastError();
+  });
+  if (rc != HM355_OK) return rc;
+  HM_CHECK(c, hipMemcpy(cost, d, sizeof(int32_t) * c->numCtus, hipMemcpyDeviceToHost));
+  return HM355_OK;
+}
+
 extern "C" int hm355_run(hm355_ctx *c, int n, const hm355_slice_desc *slices)
 {
   if (!c || !slices || n < 1 || n > (int)c->slots.size()) return HM355_ERR_ARG;
-  return run_rows_impl(c, 0, n, slices, 0, c->hp.hCtu - 1);
+  const int rc = run_rows_impl(c, 0, n, slices, 0, c->hp.hCtu - 1);
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -880,12 +1106,8 @@ extern "C" int hm355_compress_slices_inter(hm355_ctx *c, int n, const hm355_inte
   if (!c || !slices || !org || n < 1 || n > (int)c->slots.size()) return HM355_ERR_ARG;
   for (int f = 0; f < n; f++) {
     const hm355_inter_slice_desc *sd = slices + f;
-    const int isB = sd->base.slice_type == 0;
-    if (sd->base.slice_type != 1 && !isB) return fail(c, HM355_ERR_ARG, "hm355_compress_slices_inter: P (1) or B (0) slices");
-    if (sd->num_ref_idx[0] < 1 || sd->num_ref_idx[0] > 16 || (isB ? (sd->num_ref_idx[1] < 1 || sd->num_ref_idx[1] > 16) : sd->num_ref_idx[1] != 0) ||
-        sd->max_merge_cand < 1 || sd->max_merge_cand > 5 || (sd->cabac_init_type != 0 && sd->cabac_init_type != 1) ||
-        sd->col_ref_idx < 0 || sd->col_ref_idx >= sd->num_ref_idx[(isB && !sd->col_from_l0) ? 1 : 0])
-      return fail(c, HM355_ERR_ARG, "bad inter slice parameters");
+    const int rc0 = inter_desc_check(c, sd, "hm355_compress_slices_inter");
+    if (rc0 != HM355_OK) return rc0;
     for (int l = 0; l < 2; l++) for (int i = 0; i < sd->num_ref_idx[l]; i++) {
       const hm355_ref_pic *hp = sd->ref[l][i];
       if (sd->dev_ref[l][i]) continue;
@@ -901,11 +1123,7 @@ extern "C" int hm355_compress_slices_inter(hm355_ctx *c, int n, const hm355_inte
   hipError_t e = hipSuccess;
   for (int f = 0; f < n && e == hipSuccess; f++) {
     const hm355_inter_slice_desc *sd = slices + f;
-    InterPic hip; memset(&hip, 0, sizeof(hip));
-    hip.sliceType = sd->base.slice_type; hip.poc = sd->poc; hip.numRefIdx[0] = sd->num_ref_idx[0]; hip.numRefIdx[1] = sd->num_ref_idx[1];
-    hip.colFromL0 = sd->col_from_l0; hip.colRefIdx = sd->col_ref_idx; hip.tmvp = sd->tmvp; hip.mvdL1Zero = sd->mvd_l1_zero;
-    hip.maxMergeCand = sd->max_merge_cand; hip.checkLDC = sd->check_ldc; hip.cabacInitType = sd->cabac_init_type;
-    hip.lambdaMotionSAD = sd->lambda_motion_sad; hip.lambdaMotionSSE = sd->lambda_motion_sse;
+    InterPic hip; inter_pic_params(sd, &hip);
     for (int l = 0; l < 2; l++) for (int i = 0; i < sd->num_ref_idx[l] && e == hipSuccess; i++) {
       if (sd->dev_ref[l][i]) { hip.ref[l][i] = sd->dev_ref[l][i]->dev; continue; }
       const hm355_ref_pic *hp = sd->ref[l][i];
@@ -913,11 +1131,9 @@ extern "C" int hm355_compress_slices_inter(hm355_ctx *c, int n, const hm355_inte
       if (k == seen.size()) { uploaded.emplace_back(); e = upload_ref_pic(c, hp, &uploaded.back()); seen.push_back(hp); }
       hip.ref[l][i] = uploaded[k].dev;
     }
-    for (int i1 = 0; i1 < sd->num_ref_idx[1]; i1++) {            // TComSlice::setList1IdxToList0Idx
-      hip.list1ToList0[i1] = -1;
-      for (int i0 = 0; i0 < sd->num_ref_idx[0]; i0++) if (hip.ref[0][i0].poc == hip.ref[1][i1].poc) { hip.list1ToList0[i1] = i0; break; }
-    }
+    inter_pic_list1(sd, &hip);
     Slot &sl = c->slots[f];
+    sl.motionSet = 1; sl.motionSad = sd->lambda_motion_sad; sl.motionSse = sd->lambda_motion_sse;   // CTUs without a lambda of their own (hm355_set_ctu_rc)
     if (e == hipSuccess) e = dIp[f].alloc(1);
     if (e == hipSuccess) e = hipMemcpy(dIp[f], &hip, sizeof(InterPic), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = sl.imeta.ensure(c->numCtus);
@@ -1163,6 +1379,7 @@ extern "C" int hm355_upload_file_frames(hm355_ctx *c, int n, const void *const *
     Slot &sl = c->slots[f];
     HM_CHECK(c, sl.rawIn.ensure(maxBytes));
     HM_CHECK(c, hipMemcpyAsync(sl.rawIn, frames[f], bytes, hipMemcpyHostToDevice, c->lane[0].stream));
+    sl.ctusDone = 0;
     ips[f].src = sl.rawIn; ips[f].dst = NULL; ips[f].fileW = file_width; ips[f].fileH = file_height; ips[f].fileBitDepth = file_bit_depth; ips[f].fromOrg = 0;
   }
   return ingest_launch(c, n, ips, 0, P.width, P.height);

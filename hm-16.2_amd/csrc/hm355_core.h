@@ -2796,6 +2796,7 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
     if (e->im) init_est_data_inter(e, 0, 0);
   }
   const int sliceQp = e->fb.qp;
+  if (e->im) e->fb.lambdaMotionSAD = e->fb.ip->lambdaMotionSAD;   // the slice's m_uiLambdaMotionSAD (hm355_inter.h reads it from here)
   if (e->fb.dqp) {
     // cu_qp_delta: the QP of this CTU (TEncCu::xComputeQP :1154 / the rate control's, TEncSlice.cpp:767-808) replaces the slice's in the quantiser
     // parameters; its predictor is the QP of the last CU coded before it in this CTU row / slice (both neighbouring quantisation groups lie
@@ -2804,10 +2805,18 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
     const int rowStart = e->ctuX == 0 && P->wpp;
     const int q = dp->ctuQp[a];
     const int refQp = (a == 0 || rowStart) ? sliceQp : dp->out[a - 1].lastQp;
-    const int flag = a == 0 ? dp->flagIn : (rowStart ? dp->rowFlag[e->ctuY] : dp->out[a - 1].flagOut);
+    // at a row start the previous CTU is not searched yet, unless an earlier call searched it (hm355_run_ctus): then its real value
+    const int flag = a == 0 ? dp->flagIn : ((rowStart && a - 1 >= dp->firstCtu) ? dp->rowFlag[e->ctuY] : dp->out[a - 1].flagOut);
     const QpTab *t = &dp->tab[q + 12];
     e->fb.qp = q;
     for (int k = 0; k < 2; k++) { e->fb.qpPer[k] = t->qpPer[k]; e->fb.qpRem[k] = t->qpRem[k]; e->fb.rdFactor[k] = t->rdFactor[k]; for (int l = 0; l < 4; l++) e->fb.errScale[k][l] = t->errScale[k][l]; }
+    if (dp->rc) {
+      // LCU-level rate control (TEncSlice.cpp:776-808): TComRdCost::setLambda and TComTrQuant::setLambdas with the CTU's lambda, for this CTU only
+      // (e->fb is this search's copy; a team's helpers copy it from here, hm355_team.h team_adopt)
+      const CtuRc *r = dp->rc + a;
+      e->fb.lambda = r->lambda; e->fb.sqrtLambda = r->sqrtLambda; e->fb.lambdaC = r->lambdaC; e->fb.lambdaMotionSAD = r->lambdaMotionSAD;
+      for (int k = 0; k < 2; k++) e->fb.rdFactor[k] = r->rdFactor[k];
+    }
     if (hm_lane() == 0) { e->ws->dq.ctuQp = q; e->ws->dq.refQp = refQp; e->ws->dq.flag = flag; }
     HM_SYNC();
   }
@@ -2842,6 +2851,14 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
   if (e->fb.dqp) {
     const int firstZ = first_coded_cu(e), q = HM_UNI(e->ws->dq.ctuQp), refQp = HM_UNI(e->ws->dq.refQp), flag = HM_UNI(e->ws->dq.flag);
     if (hm_lane() == 0) { CtuDqp o; o.qp = (int8_t)q; o.refQp = (int8_t)refQp; o.lastQp = (int8_t)(firstZ < 256 ? q : refQp); o.flagOut = (uint8_t)flag; o.firstZ = (int16_t)firstZ; o.pad = 0; e->fb.dqp->out[a] = o; }
+    if (e->fb.dqp->rcOut) {
+      // what TEncSlice.cpp:861-887 hands TEncRateCtrl::updateAfterCTU: the CTU's bits and pCtu->getQP(0) (m_phQP of partition 0: its CU's QP when
+      // that CU has a coded block, else the predictor), or g_RCInvalidQPValue when no partition inside the picture is coded other than skip
+      int coded = 0;
+      HM_PAR_FOR(z, 256) if (e->meta.pred[z] != MODE_NONE && !(e->im && e->im->skip[z])) coded = 1;
+      coded = hm_wave_max_i(coded);
+      if (hm_lane() == 0) { CtuRcOut o; o.bits = (int32_t)e->outBits; o.qp = coded ? (firstZ > 0 ? refQp : q) : -999; e->fb.dqp->rcOut[a] = o; }
+    }
     HM_SYNC();
   }
   if (e->im) { HM_PAR_FOR(i, 32) e->fb.intMv[(size_t)a * 32 + i] = e->ws->intMv[i >> 4][i & 15]; HM_SYNC(); }   // carried to the next CTU in coding order

@@ -219,6 +219,56 @@ extern "C" __global__ void __launch_bounds__(64) hm355_preanalyze_kernel(const P
   }
 }
 
+// ---- TEncSlice::calCostSliceI (TEncSlice.cpp:606-632) with TEncCu::updateCtuDataISlice / xCalcHADs8x8_ISlice (TEncCu.cpp:1286-1399): per CTU the sum
+// of the 8x8 Hadamard costs of the ORIGINAL luma samples over every whole 8x8 block inside the picture (sum of |coefficients| minus |DC|, (s + 2) >> 2),
+// then (sum + offset) >> (bitDepth - 8): the m_costIntra the rate model reads before an I picture.  One wavefront per CTU, one lane per 8x8 block
+// (lane = 8 * block row + block column): each luma sample is read once, as one 16-byte load per block row; integer arithmetic only; butterfly reduction.
+typedef short hm_short8 __attribute__((ext_vector_type(8)));
+extern "C" __global__ void __launch_bounds__(64) hm355_intra_cost_kernel(const Params *P, int frame, int32_t *cost)
+{
+  const FrameBuf *fb = P->frames + frame;
+  const int a = (int)blockIdx.x, cx = a % P->wCtu, cy = a / P->wCtu, lane = (int)threadIdx.x;
+  const int w = P->width - cx * 64 < 64 ? P->width - cx * 64 : 64, h = P->height - cy * 64 < 64 ? P->height - cy * 64 : 64;
+  const int bx = (lane & 7) * 8, by = (lane >> 3) * 8;
+  int had = 0;
+  if (bx + 8 <= w && by + 8 <= h) {
+    // planes are padded to whole CTUs with a stride of whole CTUs: the block's rows start on 16-byte boundaries
+    const Pel *p = fb->org[0] + (size_t)(cy * 64 + by) * P->stride[0] + cx * 64 + bx;
+    int m[8][8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {        // horizontal butterflies of row j
+      const hm_short8 v = *(const hm_short8 *)(p + (size_t)j * P->stride[0]);
+      int d[8] = {v.s0, v.s1, v.s2, v.s3, v.s4, v.s5, v.s6, v.s7}, t[8];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { t[k] = d[k] + d[k + 4]; t[k + 4] = d[k] - d[k + 4]; }
+#pragma unroll
+      for (int k = 0; k < 2; k++) { d[k] = t[k] + t[k + 2]; d[k + 2] = t[k] - t[k + 2]; d[k + 4] = t[k + 4] + t[k + 6]; d[k + 6] = t[k + 4] - t[k + 6]; }
+#pragma unroll
+      for (int k = 0; k < 8; k += 2) { m[j][k] = d[k] + d[k + 1]; m[j][k + 1] = d[k] - d[k + 1]; }
+    }
+    int s = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {        // vertical butterflies of column i
+      int d[8], t[8];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { t[k] = m[k][i] + m[k + 4][i]; t[k + 4] = m[k][i] - m[k + 4][i]; }
+#pragma unroll
+      for (int k = 0; k < 2; k++) { d[k] = t[k] + t[k + 2]; d[k + 2] = t[k] - t[k + 2]; d[k + 4] = t[k + 4] + t[k + 6]; d[k + 6] = t[k + 4] - t[k + 6]; }
+#pragma unroll
+      for (int k = 0; k < 8; k += 2) {
+        const int c0 = d[k] + d[k + 1], c1 = d[k] - d[k + 1];
+        s += (c0 < 0 ? -c0 : c0) + (c1 < 0 ? -c1 : c1);
+        if (i == 0 && k == 0) s -= c0 < 0 ? -c0 : c0;    // minus |DC|
+      }
+    }
+    had = (s + 2) >> 2;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) had += __shfl_xor(had, o, 64);
+  const int shift = P->bitDepth - 8, offset = shift > 0 ? 1 << (shift - 1) : 0;
+  if (lane == 0) cost[a] = (had + offset) >> shift;
+}
+
 // ---- device-resident reference pictures: what later pictures read of a finished one ----
 // mode 0..2: border extension of plane c (TComPicYuv::extendPicBorder, TComPicYuv.cpp:171) from the slot's reconstruction into a
 //            plane with HM_REF_MARGIN (>> 1 for chroma) samples on every side; one lane per destination sample, rows contiguous.

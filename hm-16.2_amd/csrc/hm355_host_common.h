@@ -67,6 +67,18 @@ static inline void hm355_fill_slice_params(FrameBuf *f, int bitDepth, int qp, do
   }
 }
 
+// LCU-level rate control: the record of one CTU -- what TComRdCost::setLambda (TComRdCost.cpp:194-216) and TComTrQuant::setLambdas with the
+// slice's chroma weight (TEncSlice.cpp:793-803) derive from the lambda the rate model gives it, with the sign-hiding factor of its QP
+static inline CtuRc hm355_ctu_rc_record(int bitDepth, int qp, double lambda, double chromaWeight)
+{
+  FrameBuf t; memset(&t, 0, sizeof(t));
+  hm355_fill_slice_params(&t, bitDepth, qp, lambda, chromaWeight);
+  CtuRc r; memset(&r, 0, sizeof(r));
+  r.lambda = t.lambda; r.sqrtLambda = t.sqrtLambda; r.lambdaC = t.lambdaC; r.rdFactor[0] = t.rdFactor[0]; r.rdFactor[1] = t.rdFactor[1];
+  r.lambdaMotionSAD = (uint32_t)floor(65536.0 * t.sqrtLambda); r.lambdaMotionSSE = (uint32_t)floor(65536.0 * lambda);
+  return r;
+}
+
 // I-slice lambda of an all-intra GOP (TEncSlice::initEncSlice, TEncSlice.cpp:323-352) -- used by our
 // TEncSlice look-alike and by the tests; the C ABI itself takes lambda from the caller.
 static inline void hm355_intra_lambda(int qp, double *lambda, double *chromaWeight)
@@ -91,13 +103,14 @@ static inline int hm355_schedule_step(int wCtu, int hCtu, int wpp, int carryLast
   return x + 2 * y;
 }
 static inline void hm355_build_schedule(int wCtu, int hCtu, int wpp, int nFrames, std::vector<WorkItem> &items, std::vector<int> &stepStart, int carryLastRow = 0,
-                                        int firstFrame = 0, int firstRow = 0, int lastRow = -1)
-{ // rows [firstRow, lastRow] of the pictures in slots [firstFrame, firstFrame + nFrames): a band of CTU rows (the rows above it are complete)
+                                        int firstFrame = 0, int firstCtu = 0, int lastCtu = -1)
+{ // CTUs [firstCtu, lastCtu] (raster addresses, i.e. coding order) of the pictures in slots [firstFrame, firstFrame + nFrames): a band of CTUs (the
+  // CTUs before it are complete) -- whole CTU rows (hm355_run_rows), or any range (hm355_run_ctus)
   items.clear(); stepStart.clear();
-  if (lastRow < 0) lastRow = hCtu - 1;
+  if (lastCtu < 0) lastCtu = wCtu * hCtu - 1;
   const int steps = hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, wCtu - 1, hCtu - 1) + 1;
   std::vector<std::vector<WorkItem> > bucket(steps);
-  for (int y = firstRow; y <= lastRow; y++) for (int x = 0; x < wCtu; x++) { WorkItem w = {0, x, y, 0}; bucket[hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, x, y)].push_back(w); }
+  for (int a = firstCtu; a <= lastCtu; a++) { const int x = a % wCtu, y = a / wCtu; WorkItem w = {0, x, y, 0}; bucket[hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, x, y)].push_back(w); }
   for (int s = 0; s < steps; s++) {
     stepStart.push_back((int)items.size());
     for (int f = 0; f < nFrames; f++) for (size_t i = 0; i < bucket[s].size(); i++) { WorkItem w = bucket[s][i]; w.frame = firstFrame + f; items.push_back(w); }

@@ -103,12 +103,23 @@ struct CtuDqp {                      // what a searched CTU leaves for the next 
   uint8_t flagOut;                   // TEncCu::m_bEncodeDQP after its encodeCtu
   int16_t firstZ, pad;               // first CU (z order) with a coded block, 256 if none: partitions before it carry refQp, the rest qp (m_phQP)
 };
+// LCU-level rate control (TEncSlice.cpp:766-808): what TComRdCost::setLambda and TComTrQuant::setLambdas derive from the lambda the rate model
+// gives one CTU, computed on the host in double precision (hm355_fill_slice_params with the CTU's QP and lambda); the device only copies it
+struct CtuRc {
+  double lambda, sqrtLambda, lambdaC;   // m_dLambda, m_sqrtLambda, the chroma lambda of RDOQ (lambda / the slice's chroma weight)
+  int64_t rdFactor[2];                  // sign-bit-hiding factor of the CTU's QP and lambda (luma, chroma)
+  uint32_t lambdaMotionSAD, lambdaMotionSSE;   // floor(65536 sqrt(lambda)), floor(65536 lambda)
+};
+struct CtuRcOut { int32_t bits, qp; };  // updateAfterCTU's inputs (TEncSlice.cpp:861-887): getTotalBits(); getQP(0), or -999 when no partition is coded other than skip
 struct DqpPic {
   int32_t flagIn, sliceQp;           // m_bEncodeDQP on entry to the slice
   const int8_t *ctuQp;               // [numCtus] QP of every CTU (TEncCu::xComputeQP / TEncRateCtrl::getRCQP)
   CtuDqp *out;                       // [numCtus]
   const uint8_t *rowFlag;            // [hCtu] WaveFrontSynchro: m_bEncodeDQP assumed at the first CTU of each row (checked by the host afterwards)
   QpTab tab[64];                     // indexed by QP + 12
+  const CtuRc *rc;                   // [numCtus] lambda of every CTU; NULL: the slice's
+  CtuRcOut *rcOut;                   // [numCtus] rate-control feedback of every searched CTU; NULL: not kept
+  int32_t firstCtu, pad;             // CTUs before it were searched by an earlier call: a row start takes their real m_bEncodeDQP, not rowFlag
 };
 
 // lookup tables generated on the host at create time (scan orders: TComRom.cpp:52-225)
@@ -135,6 +146,7 @@ struct FrameBuf {
   double errScale[2][4];             // [luma/chroma][log2-2]  TComTrQuant::setErrScaleCoeff :2933
   int64_t rdFactor[2];               // sign-bit-hiding factor  TComTrQuant.cpp:2382-2386
   int32_t qp, qpPer[2], qpRem[2];
+  uint32_t lambdaMotionSAD;          // TComRdCost::m_uiLambdaMotionSAD of the CTU under search (process_ctu: the slice's, or the rate control's for the CTU)
 };
 
 struct Params {

@@ -74,13 +74,23 @@ class DqpDesc(C.Structure):
     _fields_ = [("use_dqp", C.c_int32), ("dqp_flag_in", C.c_int32), ("ctu_qp", C.c_void_p)]
 
 
+class CtuRc(C.Structure):
+    """hm355_ctu_rc: what TEncRateCtrl::updateAfterCTU takes for one CTU (getTotalBits(); getQP(0), or -999)"""
+    _fields_ = [("bits", C.c_int32), ("qp", C.c_int32)]
+
+
+CTU_RC_DTYPE = np.dtype([("bits", "<i4"), ("qp", "<i4")])
+assert CTU_RC_DTYPE.itemsize == C.sizeof(CtuRc)
+
+
 class BitsDesc(C.Structure):
     _fields_ = [("slice_type", C.c_int32), ("qp", C.c_int32), ("cabac_init_type", C.c_int32), ("num_ref_idx", C.c_int32 * 2), ("mvd_l1_zero", C.c_int32),
                 ("max_merge_cand", C.c_int32), ("sao_enabled", C.c_int32 * 2), ("out", C.c_void_p), ("out_cap", C.c_size_t), ("sub_sizes", C.c_void_p),
                 ("next_cabac_init_type", C.c_int32), ("num_bins", C.c_uint32)]
 
 
-EXPORTS = ["hm355_build_id", "hm355_set_dqp", "hm355_get_dqp", "hm355_preanalyze", "hm355_create", "hm355_destroy", "hm355_last_error", "hm355_compress_slice", "hm355_compress_slices",
+EXPORTS = ["hm355_build_id", "hm355_set_dqp", "hm355_get_dqp", "hm355_preanalyze", "hm355_set_ctu_rc", "hm355_slice_begin", "hm355_slice_begin_inter",
+           "hm355_run_ctus", "hm355_ctu_rc_feedback", "hm355_download_inter", "hm355_slice_end", "hm355_intra_cost","hm355_create", "hm355_destroy", "hm355_last_error", "hm355_compress_slice", "hm355_compress_slices",
            "hm355_compress_slice_inter", "hm355_compress_slices_inter", "hm355_deblock", "hm355_deblock_run", "hm355_ref_from_slot", "hm355_ref_release", "hm355_ref_bytes", "hm355_ref_export", "hm355_ref_import", "hm355_sao_run",
            "hm355_num_substreams", "hm355_encode_slices_run", "hm355_encode_slice",
            "hm355_upload_file_frames", "hm355_download_file_frames", "hm355_download_org",
@@ -112,6 +122,14 @@ def load_library(path=LIB_PATH):
     lib.hm355_set_dqp.argtypes = [C.c_void_p, C.c_int, C.POINTER(DqpDesc)]
     lib.hm355_get_dqp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
     lib.hm355_preanalyze.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.hm355_set_ctu_rc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hm355_slice_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(SliceDesc)]
+    lib.hm355_slice_begin_inter.argtypes = [C.c_void_p, C.c_int, C.POINTER(InterSliceDesc)]
+    lib.hm355_run_ctus.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.hm355_ctu_rc_feedback.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]     # hm355_ctu_rc *: CTU_RC_DTYPE records
+    lib.hm355_download_inter.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.hm355_slice_end.argtypes = [C.c_void_p, C.c_int]
+    lib.hm355_intra_cost.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.hm355_download.argtypes = [C.c_void_p, C.c_int, C.POINTER(Planes), C.c_void_p, C.POINTER(SliceStats)]
     lib.hm355_run_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SliceDesc), C.c_int, C.c_int]
     lib.hm355_boundary_bytes.argtypes = [C.c_void_p]
@@ -258,6 +276,71 @@ class Encoder:
         wc = (self.w + 63) // 64
         n = np.array([min(64, self.w - (a % wc) * 64) * min(64, self.h - (a // wc) * 64) for a in range(self.num_ctus)], np.uint64)
         return np.concatenate([s, n[:, None]], axis=1)
+
+    # ---- LCU-level rate control (include/hm355.h): a QP and a lambda per CTU, the slice searched CTU range by CTU range ----
+    def set_ctu_rc(self, slot, first_ctu, qp, lam=None):
+        """hm355_set_ctu_rc: QP (int8) and lambda (float64, or None: the slice lambda) of CTUs [first_ctu, first_ctu + len(qp))"""
+        q = np.ascontiguousarray(qp, np.int8).reshape(-1)
+        l = np.ascontiguousarray(lam, np.float64).reshape(-1) if lam is not None else None
+        assert l is None or len(l) == len(q)
+        self._check(self.lib.hm355_set_ctu_rc(self.h_, slot, int(first_ctu), len(q), q.ctypes.data, l.ctypes.data if l is not None else None),
+                    "hm355_set_ctu_rc")
+
+    def slice_begin(self, slot, qp, lam, chroma_weight):
+        """hm355_slice_begin: an I slice on a slot whose original is in HBM (upload first)"""
+        sd = SliceDesc(2, int(qp), float(lam), float(chroma_weight))
+        self._check(self.lib.hm355_slice_begin(self.h_, slot, C.byref(sd)), "hm355_slice_begin")
+
+    def slice_begin_inter(self, slot, slice_params, ref_pics):
+        """hm355_slice_begin_inter: a P / B slice (slice_params as for compress_inter) on a slot whose original is in HBM; ref_pics {poc: {"dev": handle}}
+        from ref_from_slot (a host picture dict is passed through as hm355_ref_pic, which the library refuses)"""
+        s = InterSliceDesc()
+        sp = slice_params
+        s.base = SliceDesc(int(sp.get("slice_type", 1)), int(sp["qp"]), float(sp["lambda"]), float(sp["chroma_weight"]))
+        s.poc, s.cabac_init_type = int(sp["poc"]), int(sp["cabac_init_type"])
+        keep = []
+        for l in range(2):
+            s.num_ref_idx[l] = int(sp["num_ref_idx"][l])
+            for i in range(s.num_ref_idx[l]):
+                f = ref_pics[int(sp["ref_poc"][l][i])]
+                if "dev" in f:
+                    s.dev_ref[l][i] = f["dev"]
+                else:
+                    pl = [np.ascontiguousarray(p, np.uint16) for p in f["rec"]]
+                    r = RefPic(); r.poc = int(sp["ref_poc"][l][i]); r.slice_type = int(f["slice_type"])
+                    for c in range(3):
+                        r.plane[c] = pl[c].ctypes.data
+                    keep += pl + [r]
+                    s.ref[l][i] = C.pointer(r)
+        for key in ("col_from_l0", "col_ref_idx", "tmvp", "mvd_l1_zero", "max_merge_cand", "check_ldc", "lambda_motion_sad", "lambda_motion_sse"):
+            setattr(s, key, int(sp[key]))
+        self._check(self.lib.hm355_slice_begin_inter(self.h_, slot, C.byref(s)), "hm355_slice_begin_inter")
+        del keep
+
+    def run_ctus(self, first_slot, n, first_ctu, num_ctus):
+        """hm355_run_ctus: CTUs [first_ctu, first_ctu + num_ctus) of the open slices of slots [first_slot, first_slot + n), one launch"""
+        self._check(self.lib.hm355_run_ctus(self.h_, first_slot, n, int(first_ctu), int(num_ctus)), "hm355_run_ctus")
+
+    def ctu_rc_feedback(self, slot, first_ctu, n):
+        """hm355_ctu_rc_feedback -> CTU_RC_DTYPE [n]: bits and QP (or -999) of CTUs [first_ctu, first_ctu + n)"""
+        out = np.zeros(n, CTU_RC_DTYPE)
+        self._check(self.lib.hm355_ctu_rc_feedback(self.h_, slot, int(first_ctu), int(n), out.ctypes.data), "hm355_ctu_rc_feedback")
+        return out
+
+    def download_inter(self, slot):
+        """hm355_download_inter -> CTU_INTER_DTYPE [numCtus]: the motion data of the slot"""
+        out = np.zeros(self.num_ctus, CTU_INTER_DTYPE)
+        self._check(self.lib.hm355_download_inter(self.h_, slot, out.ctypes.data), "hm355_download_inter")
+        return out
+
+    def slice_end(self, slot):
+        self._check(self.lib.hm355_slice_end(self.h_, slot), "hm355_slice_end")
+
+    def intra_cost(self, slot):
+        """hm355_intra_cost -> int32 [numCtus]: TEncSlice::calCostSliceI's m_costIntra of every CTU of the slot's original"""
+        out = np.zeros(self.num_ctus, np.int32)
+        self._check(self.lib.hm355_intra_cost(self.h_, slot, out.ctypes.data), "hm355_intra_cost")
+        return out
 
     def run_begin(self, lane, first_slot, n, qp):
         """enqueue the search over slots [first_slot, first_slot + n) on pipeline lane `lane`; returns at once (hm355_run_begin)"""

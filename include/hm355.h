@@ -227,6 +227,36 @@ int hm355_set_dqp(hm355_ctx *ctx, int slot, const hm355_dqp_desc *desc);
 int hm355_get_dqp(hm355_ctx *ctx, int slot, int8_t *qp_out, int32_t *dqp_flag_out);
 int hm355_preanalyze(hm355_ctx *ctx, int slot, uint64_t *sums);
 
+/* ---- LCU-level rate control (--RateControl=1, LCULevelRateControl on: TEncSlice.cpp:766-887).  Before each CTU the caller's rate model
+ * (TEncRateCtrl, which stays with the caller) gives it a lambda and a QP; after it, updateAfterCTU takes the CTU's bits and QP -- so the QP of
+ * CTU n depends on the bits of CTUs 0..n-1, and the slice is searched CTU range by CTU range with the model in between.
+ * hm355_set_ctu_rc: QP and lambda of CTUs [first_ctu, first_ctu + n) of a slot armed with hm355_set_dqp (use_dqp 1); QPs in [-QpBDOffset, 51],
+ * lambdas in [1e-4, 65535] (what the motion lambda's 32 bits hold; TEncRateCtrl clips to [0.1, 10000]); lambda NULL: the slice lambda.  What TComRdCost::setLambda / TComTrQuant::setLambdas derive from a lambda (its
+ * square root, the chroma lambda = lambda / the slice's chroma weight, the motion lambdas, the sign-hiding factor of the CTU's QP) is computed on
+ * the host in double precision.  Honoured by every search entry on that slot (hm355_run, hm355_compress_slice(s)(_inter), hm355_run_ctus) until
+ * hm355_set_dqp is called again.
+ * Slice-resident search: hm355_slice_begin (I) / hm355_slice_begin_inter (P / B; device-resident references dev_ref only) opens a slice on an
+ * armed slot (hm355_set_dqp first; it is refused while the slice is open) whose original is already in HBM (hm355_upload, hm355_upload_file_frames);
+ * hm355_run_ctus searches CTUs [first_ctu, first_ctu + num_ctus) in coding order in slots [first_slot, first_slot + n), one launch: first_ctu must
+ * equal the number of CTUs already searched in the slice (hm355_slice_begin* sets it to 0).  Under WaveFrontSynchro the first CTU of a row takes the real
+ * m_bEncodeDQP of the CTU an earlier call finished.  hm355_ctu_rc_feedback reads back 8 bytes per CTU: getTotalBits() and getQP(0), or -999
+ * (g_RCInvalidQPValue) when no partition inside the picture is coded other than skip -- for CTUs the last search of the slot's picture (any search
+ * entry; an upload starts a new picture) reached with the slot armed.
+ * hm355_download / hm355_download_inter return the CTU data; after hm355_slice_end the slot allows what a slot searched by
+ * hm355_compress_slices_inter allows (hm355_deblock_run, hm355_sao_run, hm355_encode_slices_run, hm355_ref_from_slot).  Lane 0.
+ * hm355_intra_cost: TEncSlice::calCostSliceI (TEncSlice.cpp:606-632) on the slot's original luma: cost[a] = m_costIntra of CTU a (the sum of
+ * the 8x8 Hadamard costs of the whole 8x8 blocks inside the picture, rounded to 8 bits), what TEncRCPic::setTotalIntraCost adds up before an
+ * I picture. ---- */
+typedef struct { int32_t bits; int32_t qp; } hm355_ctu_rc;     /* pCtu->getTotalBits(); pCtu->getQP(0) or -999 */
+int hm355_set_ctu_rc(hm355_ctx *ctx, int slot, int first_ctu, int n, const int8_t *qp, const double *lambda);
+int hm355_slice_begin(hm355_ctx *ctx, int slot, const hm355_slice_desc *sd);
+int hm355_slice_begin_inter(hm355_ctx *ctx, int slot, const hm355_inter_slice_desc *sd);
+int hm355_run_ctus(hm355_ctx *ctx, int first_slot, int n, int first_ctu, int num_ctus);
+int hm355_ctu_rc_feedback(hm355_ctx *ctx, int slot, int first_ctu, int n, hm355_ctu_rc *out);
+int hm355_download_inter(hm355_ctx *ctx, int slot, hm355_ctu_inter_out *ictus);
+int hm355_slice_end(hm355_ctx *ctx, int slot);
+int hm355_intra_cost(hm355_ctx *ctx, int slot, int32_t *cost);
+
 /* ---- device-resident variant (what bench.py times: inputs already in HBM) ----
  * Upload / run / download are separate so that a caller can keep pictures resident. */
 int hm355_upload(hm355_ctx *ctx, int slot, const hm355_planes *org);          /* host -> HBM picture slot */
