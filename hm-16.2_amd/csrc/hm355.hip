@@ -436,12 +436,7 @@ static int dqp_prepare(hm355_ctx *c, int slot, const hm355_slice_desc *sd, hipSt
   DqpPic *hp = new DqpPic; memset(hp, 0, sizeof(*hp));
   hp->flagIn = sl.dqpFlagIn; hp->sliceQp = sd->qp; hp->ctuQp = sl.dCtuQp; hp->out = sl.dDqpOut; hp->rowFlag = sl.dRowFlag;
   hp->rcOut = sl.dRcOut; hp->firstCtu = 0;
-  for (int q = -12; q <= 51; q++) {
-    FrameBuf t; memset(&t, 0, sizeof(t));
-    hm355_fill_slice_params(&t, P.bitDepth, q, sd->lambda, sd->chroma_weight);
-    QpTab &e = hp->tab[q + 12];
-    for (int k = 0; k < 2; k++) { e.qpPer[k] = t.qpPer[k]; e.qpRem[k] = t.qpRem[k]; e.rdFactor[k] = t.rdFactor[k]; for (int l = 0; l < 4; l++) e.errScale[k][l] = t.errScale[k][l]; }
-  }
+  hm355_fill_qp_tab(hp->tab, P.bitDepth, sd->lambda, sd->chroma_weight);
   std::vector<int8_t> q(c->numCtus, (int8_t)sd->qp);
   if (!sl.ctuQp.empty()) for (int a = 0; a < c->numCtus; a++) if (sl.ctuQp[a] != HM_QP_SLICE) q[a] = sl.ctuQp[a];
   int anyLambda = 0;

@@ -67,6 +67,17 @@ static inline void hm355_fill_slice_params(FrameBuf *f, int bitDepth, int qp, do
   }
 }
 
+// cu_qp_delta: the quantiser state of every QP a coding unit may take (-12..51, entry q + 12 of DqpPic::tab) under the slice's lambda and chroma weight
+static inline void hm355_fill_qp_tab(QpTab tab[64], int bitDepth, double lambda, double chromaWeight)
+{
+  for (int q = -12; q <= 51; q++) {
+    FrameBuf t; memset(&t, 0, sizeof(t));
+    hm355_fill_slice_params(&t, bitDepth, q, lambda, chromaWeight);
+    QpTab &e = tab[q + 12];
+    for (int k = 0; k < 2; k++) { e.qpPer[k] = t.qpPer[k]; e.qpRem[k] = t.qpRem[k]; e.rdFactor[k] = t.rdFactor[k]; for (int l = 0; l < 4; l++) e.errScale[k][l] = t.errScale[k][l]; }
+  }
+}
+
 // LCU-level rate control: the record of one CTU -- what TComRdCost::setLambda (TComRdCost.cpp:194-216) and TComTrQuant::setLambdas with the
 // slice's chroma weight (TEncSlice.cpp:793-803) derive from the lambda the rate model gives it, with the sign-hiding factor of its QP
 static inline CtuRc hm355_ctu_rc_record(int bitDepth, int qp, double lambda, double chromaWeight)

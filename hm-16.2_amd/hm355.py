@@ -175,6 +175,20 @@ def intra_lambda(qp):
     return lam, 2.0 ** ((qp - qpc) / 3.0)
 
 
+def inter_slice_params(kind, qp, lam, poc, num_ref_idx, ref_poc, **overrides):
+    """Slice parameters of a synthetic "P" or "B" slice in the form Encoder.compress_inter* / slice_begin_inter take: the caller's lambda (the
+    configurations derive it from the QP in different ways) with the motion lambdas TComRdCost::setLambda (TComRdCost.cpp:194-216) takes from it,
+    the chroma weight of the QP, and low-delay defaults for the rest, which `overrides` replaces key by key."""
+    import math
+    sp = dict(slice_type=1 if kind == "P" else 0, qp=qp, chroma_weight=intra_lambda(qp)[1], poc=poc, cabac_init_type=1 if kind == "P" else 0,
+              num_ref_idx=num_ref_idx, ref_poc=ref_poc, col_from_l0=1, col_ref_idx=0, tmvp=1, mvd_l1_zero=0, max_merge_cand=5, check_ldc=1,
+              lambda_motion_sad=int(math.floor(65536.0 * math.sqrt(lam))), lambda_motion_sse=int(math.floor(65536.0 * lam)))
+    sp["lambda"] = lam
+    assert set(overrides) <= set(sp), f"unknown slice parameter {sorted(set(overrides) - set(sp))}"
+    sp.update(overrides)
+    return sp
+
+
 def aq_activities(sums):
     """TEncPreanalyzer::xPreanalyze (TEncPreanalyzer.cpp:117-137) from the per-CTU quadrant sums hm355_preanalyze returns: activity per CTU
     (1 + the smallest quadrant "variance", every quadrant's sums divided by the sample count of the WHOLE unit, as the reference does) and
@@ -212,6 +226,50 @@ def _planes(arrs):
         assert a.dtype == np.uint16 and a.flags["C_CONTIGUOUS"]
         p.plane[k] = a.ctypes.data_as(C.POINTER(C.c_uint16))
     return p
+
+
+def _ref_pic(poc, f):
+    """one host reference-picture dict (see Encoder.compress_inter_batch) -> (hm355_ref_pic, the arrays it points into)"""
+    pl = [np.ascontiguousarray(p, np.uint16) for p in f["rec"]]
+    pm = np.ascontiguousarray(f["pred_mode"], np.uint8)
+    mv = [np.ascontiguousarray(f["mv"][l], np.int16) for l in range(2)]
+    ri = [np.ascontiguousarray(f["ref_idx"][l], np.int8) for l in range(2)]
+    r = RefPic()
+    r.poc, r.slice_type, r.long_term = int(poc), int(f["slice_type"]), 0
+    for c in range(3):
+        r.plane[c] = pl[c].ctypes.data
+    r.pred_mode = pm.ctypes.data
+    for l in range(2):
+        r.mv[l] = mv[l].ctypes.data; r.ref_idx[l] = ri[l].ctypes.data; r.num_ref[l] = int(f["num_ref_idx"][l])
+        for i in range(16):
+            r.ref_poc[l][i] = int(f["ref_poc"][l][i]); r.ref_lt[l][i] = int(f["ref_long_term"][l][i])
+    return r, pl + [pm] + mv + ri
+
+
+def _inter_slice_desc(slice_params, ref_pics, conv=None):
+    """(slice_params, ref_pics) as Encoder.compress_inter_batch takes them -> (hm355_inter_slice_desc, the objects it points into: the caller
+    holds them until the library call returns).  conv: a dict shared by the descriptors of one call, so that a ref_pics dict object that several
+    of them use is converted once -- they then point at the same hm355_ref_pic records, which the library uploads once."""
+    sp = slice_params
+    refs, keep = ({} if conv is None else conv).setdefault(id(ref_pics), ({}, []))
+    s = InterSliceDesc()
+    s.base = SliceDesc(int(sp.get("slice_type", 1)), int(sp["qp"]), float(sp["lambda"]), float(sp["chroma_weight"]))
+    s.poc, s.cabac_init_type = int(sp["poc"]), int(sp["cabac_init_type"])
+    for l in range(2):
+        s.num_ref_idx[l] = int(sp["num_ref_idx"][l])
+        for i in range(s.num_ref_idx[l]):
+            poc = int(sp["ref_poc"][l][i])
+            f = ref_pics[poc]
+            if "dev" in f:                           # device-resident reference (ref_from_slot)
+                s.dev_ref[l][i] = f["dev"]
+                continue
+            if poc not in refs:
+                refs[poc], arrays = _ref_pic(poc, f)
+                keep += arrays + [refs[poc]]
+            s.ref[l][i] = C.pointer(refs[poc])
+    for key in ("col_from_l0", "col_ref_idx", "tmvp", "mvd_l1_zero", "max_merge_cand", "check_ldc", "lambda_motion_sad", "lambda_motion_sse"):
+        setattr(s, key, int(sp[key]))
+    return s, keep
 
 
 class Encoder:
@@ -294,26 +352,7 @@ class Encoder:
     def slice_begin_inter(self, slot, slice_params, ref_pics):
         """hm355_slice_begin_inter: a P / B slice (slice_params as for compress_inter) on a slot whose original is in HBM; ref_pics {poc: {"dev": handle}}
         from ref_from_slot (a host picture dict is passed through as hm355_ref_pic, which the library refuses)"""
-        s = InterSliceDesc()
-        sp = slice_params
-        s.base = SliceDesc(int(sp.get("slice_type", 1)), int(sp["qp"]), float(sp["lambda"]), float(sp["chroma_weight"]))
-        s.poc, s.cabac_init_type = int(sp["poc"]), int(sp["cabac_init_type"])
-        keep = []
-        for l in range(2):
-            s.num_ref_idx[l] = int(sp["num_ref_idx"][l])
-            for i in range(s.num_ref_idx[l]):
-                f = ref_pics[int(sp["ref_poc"][l][i])]
-                if "dev" in f:
-                    s.dev_ref[l][i] = f["dev"]
-                else:
-                    pl = [np.ascontiguousarray(p, np.uint16) for p in f["rec"]]
-                    r = RefPic(); r.poc = int(sp["ref_poc"][l][i]); r.slice_type = int(f["slice_type"])
-                    for c in range(3):
-                        r.plane[c] = pl[c].ctypes.data
-                    keep += pl + [r]
-                    s.ref[l][i] = C.pointer(r)
-        for key in ("col_from_l0", "col_ref_idx", "tmvp", "mvd_l1_zero", "max_merge_cand", "check_ldc", "lambda_motion_sad", "lambda_motion_sse"):
-            setattr(s, key, int(sp[key]))
+        s, keep = _inter_slice_desc(slice_params, ref_pics)
         self._check(self.lib.hm355_slice_begin_inter(self.h_, slot, C.byref(s)), "hm355_slice_begin_inter")
         del keep
 
@@ -411,49 +450,13 @@ class Encoder:
         ref_pics: {poc: dict(slice_type, rec=[3 planes], pred_mode, mv=[2], ref_idx=[2], num_ref_idx, ref_poc, ref_long_term)}
         (a ref_pics dict object shared by several jobs is uploaded once).  Returns [(rec planes, ctus, inter ctus, stats)]."""
         n = len(jobs)
-        keep, conv = [], {}
+        conv = {}                                    # holds what the descriptors point into until the call has returned
         descs = (InterSliceDesc * n)()
         orgs, recs, po, pr = [], [], (Planes * n)(), (Planes * n)()
         ctus = [np.zeros(self.num_ctus, CTU_DTYPE) for _ in range(n)]
         ictus = [np.zeros(self.num_ctus, CTU_INTER_DTYPE) for _ in range(n)]
         for k, (planes, sp, ref_pics) in enumerate(jobs):
-            if id(ref_pics) not in conv:
-                refs = {}
-                for poc, f in ref_pics.items():
-                    if "dev" in f:                           # device-resident reference (ref_from_slot)
-                        refs[int(poc)] = f["dev"]
-                        continue
-                    pl = [np.ascontiguousarray(p, np.uint16) for p in f["rec"]]
-                    pm = np.ascontiguousarray(f["pred_mode"], np.uint8)
-                    mv = [np.ascontiguousarray(f["mv"][l], np.int16) for l in range(2)]
-                    ri = [np.ascontiguousarray(f["ref_idx"][l], np.int8) for l in range(2)]
-                    keep += pl + [pm] + mv + ri
-                    r = RefPic()
-                    r.poc, r.slice_type, r.long_term = int(poc), int(f["slice_type"]), 0
-                    for c in range(3):
-                        r.plane[c] = pl[c].ctypes.data
-                    r.pred_mode = pm.ctypes.data
-                    for l in range(2):
-                        r.mv[l] = mv[l].ctypes.data; r.ref_idx[l] = ri[l].ctypes.data; r.num_ref[l] = int(f["num_ref_idx"][l])
-                        for i in range(16):
-                            r.ref_poc[l][i] = int(f["ref_poc"][l][i]); r.ref_lt[l][i] = int(f["ref_long_term"][l][i])
-                    refs[int(poc)] = r
-                conv[id(ref_pics)] = refs
-            refs = conv[id(ref_pics)]
-            s = descs[k]
-            s.base = SliceDesc(int(sp.get("slice_type", 1)), int(sp["qp"]), float(sp["lambda"]), float(sp["chroma_weight"]))
-            s.poc, s.cabac_init_type = int(sp["poc"]), int(sp["cabac_init_type"])
-            for l in range(2):
-                s.num_ref_idx[l] = int(sp["num_ref_idx"][l])
-                for i in range(s.num_ref_idx[l]):
-                    rr = refs[int(sp["ref_poc"][l][i])]
-                    if isinstance(rr, RefPic):
-                        s.ref[l][i] = C.pointer(rr)
-                    else:
-                        s.dev_ref[l][i] = rr
-            for key in ("col_from_l0", "col_ref_idx", "tmvp", "mvd_l1_zero", "max_merge_cand", "check_ldc", "lambda_motion_sad",
-                        "lambda_motion_sse"):
-                setattr(s, key, int(sp[key]))
+            descs[k], _ = _inter_slice_desc(sp, ref_pics, conv)
             org = [np.ascontiguousarray(p, np.uint16) for p in planes]
             rec = [np.zeros_like(p) for p in org]
             orgs.append(org); recs.append(rec)
@@ -462,7 +465,7 @@ class Encoder:
         pi = (C.c_void_p * n)(*[a.ctypes.data for a in ictus])
         st = (SliceStats * n)()
         self._check(self.lib.hm355_compress_slices_inter(self.h_, n, descs, po, pr, pc, pi, st), "hm355_compress_slices_inter")
-        del keep
+        del conv
         return [(recs[k], ctus[k], ictus[k], (st[k].pic_total_bits, st[k].pic_rd_cost, st[k].pic_dist)) for k in range(n)]
 
     def compress_inter(self, planes, slice_params, ref_pics):

@@ -8,6 +8,14 @@ META_FIELDS = ["depth", "part_size", "pred_mode", "intra_dir_luma", "intra_dir_c
 CASES = ["c1_416x240_8b_qp32", "wpp_416x240_10b_qp32", "small_192x136_8b_qp22", "small_128x128_10b_qp37", "wpp_256x192_8b_qp27"]
 
 
+def build_hostsim(tmp_path, name, *flags, exe=None):
+    """compiles the host twin tests/hostsim/<name>.cpp into tmp_path (as `exe`, by default `name`) and returns the program's path"""
+    import subprocess
+    out = tmp_path / (exe or name)
+    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-w", *flags, "-o", str(out), os.path.join(ROOT, "tests", "hostsim", name + ".cpp")], check=True)
+    return out
+
+
 def load_case(name):
     g = np.load(os.path.join(GOLD, name + ".npz"))
     cfg = {k: int(g[k]) for k in ("width", "height", "bit_depth", "frames", "qp", "wpp", "seed")}
@@ -150,11 +158,14 @@ def assert_inter_ctus_equal(ctus, ictus, want, what):
             assert np.array_equal(ictus[f][:, l], want[g % l]), f"{what}: {g % l} differs"
 
 
-def ldp_slice_inputs(r, finals):
-    """(slice_params, ref_pics) in the form hm355.Encoder.compress_inter takes, from an 'S' record and the 'F' records"""
+def ldp_slice_inputs(r, finals, refs=None):
+    """(slice_params, ref_pics) in the form hm355.Encoder.compress_inter takes, from an 'S' record and the 'F' records -- or, instead of the
+    host pictures of `finals`, the ready-made `refs` ({poc: device-resident reference})"""
     sp = {k: r[k] for k in ("slice_type", "qp", "lambda", "poc", "cabac_init_type", "num_ref_idx", "ref_poc", "col_from_l0", "col_ref_idx", "tmvp",
                             "mvd_l1_zero", "max_merge_cand", "check_ldc", "lambda_motion_sad", "lambda_motion_sse")}
     sp["chroma_weight"] = r["weight_cb"]
+    if refs is not None:
+        return sp, refs
     refs = {}
     for poc in set(int(r["ref_poc"][l][i]) for l in range(2) for i in range(r["num_ref_idx"][l])):
         f = finals[poc]; m = f["motion"]

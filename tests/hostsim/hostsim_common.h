@@ -1,0 +1,66 @@
+// DEBUGGING AID, NOT PRODUCT: what the host twins (hostsim.cpp, hostsim_inter.cpp, hostsim_rc.cpp) share -- the kernel source compiled for the
+// host with one "lane", Params and FrameBuf set up as the library sets them up, planar YUV input, and the HMD1 dump of the oracle CLI.
+// Everything the twins and the library must agree on is not here but in hm355_host_common.h, which both call.
+#pragma once
+#define HM355_HOSTSIM 1
+#include "../../hm-16.2_amd/csrc/hm355_core.h"
+#include "../../hm-16.2_amd/csrc/hm355_host_common.h"
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+
+// sequence parameters, lookup tables and one lane's workspace
+static inline void hostsim_params(Params &P, int w, int h, int bd, int wpp)
+{
+  memset(&P, 0, sizeof(P));
+  P.width = w; P.height = h; P.bitDepth = bd; P.wpp = wpp; P.wCtu = (w + 63) / 64; P.hCtu = (h + 63) / 64;
+  P.stride[0] = P.wCtu * 64; P.stride[1] = P.stride[2] = P.wCtu * 32;
+  Tables *tab = new Tables; hm355_build_tables(tab); P.tab = tab;
+  P.ws = (WorkSpace *)calloc(1, sizeof(WorkSpace));
+}
+static inline size_t hostsim_plane_samples(const Params &P, int c) { return (size_t)P.stride[c] * P.hCtu * (c ? 32 : 64); }
+
+// zero-filled planes (padded to whole CTUs) and per-CTU arrays of one picture
+static inline void hostsim_alloc_frame(FrameBuf &fb, const Params &P)
+{
+  const int nctu = P.wCtu * P.hCtu;
+  memset(&fb, 0, sizeof(fb));
+  for (int c = 0; c < 3; c++) { fb.org[c] = (Pel *)calloc(hostsim_plane_samples(P, c), sizeof(Pel)); fb.rec[c] = (Pel *)calloc(hostsim_plane_samples(P, c), sizeof(Pel)); }
+  fb.meta = (CtuMeta *)calloc(nctu, sizeof(CtuMeta)); fb.coef = (TCoeff *)calloc((size_t)nctu * HM_COEF_CTU, sizeof(TCoeff));
+  fb.stat = (CtuStat *)calloc(nctu, sizeof(CtuStat)); fb.endState = (Cabac *)calloc(nctu, sizeof(Cabac));
+}
+
+// the next picture of a planar 4:2:0 file (8 bit: bytes, otherwise little-endian 16 bit) into fb.org; false when the file ends early
+static inline bool hostsim_read_yuv(FILE *fi, FrameBuf &fb, const Params &P)
+{
+  for (int c = 0; c < 3; c++) {
+    const int pw = P.width >> (c ? 1 : 0), ph = P.height >> (c ? 1 : 0);
+    for (int y = 0; y < ph; y++) for (int x = 0; x < pw; x++) {
+      unsigned v;
+      if (P.bitDepth == 8) { unsigned char t; if (fread(&t, 1, 1, fi) != 1) return false; v = t; } else { unsigned short t; if (fread(&t, 2, 1, fi) != 1) return false; v = t; }
+      fb.org[c][y * P.stride[c] + x] = (Pel)v;
+    }
+  }
+  return true;
+}
+
+// the HMD1 dump (same as the oracle CLI's): header, then per picture the cost / bits / distortion, decisions and coefficients of every CTU and the reconstruction
+static inline void hostsim_write_hmd1_header(FILE *fo, const Params &P, int frames)
+{
+  fwrite("HMD1", 1, 4, fo);
+  uint32_t hdr[5] = { (uint32_t)P.width, (uint32_t)P.height, (uint32_t)P.bitDepth, 64, (uint32_t)frames }; fwrite(hdr, 4, 5, fo);
+}
+static inline void hostsim_write_hmd1_picture(FILE *fo, const Params &P, const FrameBuf &fb, int f)
+{
+  const int nctu = P.wCtu * P.hCtu;
+  uint32_t u[2] = { (uint32_t)f, (uint32_t)nctu }; fwrite(u, 4, 2, fo);
+  for (int a = 0; a < nctu; a++) {
+    fwrite(&fb.stat[a].cost, 8, 1, fo); fwrite(&fb.stat[a].bits, 4, 1, fo); fwrite(&fb.stat[a].dist, 4, 1, fo);
+    fwrite(&fb.meta[a], 1, sizeof(CtuMeta), fo);
+    fwrite(fb.coef + (size_t)a * HM_COEF_CTU, 4, HM_COEF_CTU, fo);
+  }
+  for (int c = 0; c < 3; c++) {
+    const int pw = P.width >> (c ? 1 : 0), ph = P.height >> (c ? 1 : 0);
+    for (int y = 0; y < ph; y++) for (int x = 0; x < pw; x++) { unsigned short v = (unsigned short)fb.rec[c][y * P.stride[c] + x]; fwrite(&v, 2, 1, fo); }
+  }
+}

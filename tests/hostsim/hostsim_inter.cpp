@@ -4,13 +4,8 @@
 //   hostsim_inter <in.yuv> <dump2.bin> <w> <h> <bitdepth> [wpp]   exit code 0 = every inter slice bit-exact
 // 'B' records (with the 'A' record of the same picture in front, tests/hmd2.py write(bits=True)) also replay the bitstream pass
 // (hm355_bits_kernel.h) on the CTU data of the preceding 'S' record, I slices included, and compare the substream bytes.
-#define HM355_HOSTSIM 1
-#include "../../hm-16.2_amd/csrc/hm355_core.h"
+#include "hostsim_common.h"
 #include "../../hm-16.2_amd/csrc/hm355_bits_kernel.h"
-#include "../../hm-16.2_amd/csrc/hm355_host_common.h"
-#include <stdio.h>
-#include <stdlib.h>
-#include <vector>
 #include <map>
 
 struct FinalPic { int poc, sliceType; std::vector<Pel> buf[3]; int stride[3]; int numRef[2]; int refPoc[2][16], refLT[2][16]; std::vector<uint8_t> pm; std::vector<MvD> mv[2]; std::vector<int8_t> ri[2]; };
@@ -27,12 +22,8 @@ int main(int argc, char **argv)
   fseek(fd, 0, SEEK_END); g_n = ftell(fd); fseek(fd, 0, SEEK_SET);
   std::vector<unsigned char> data(g_n); if (fread(data.data(), 1, g_n, fd) != g_n) return 1;
   g_p = data.data(); g_off = 4;
-  Params P; memset(&P, 0, sizeof(P));
-  P.width = w; P.height = h; P.bitDepth = bd; P.wpp = argc > 6 ? atoi(argv[6]) : 0; P.wCtu = (w + 63) / 64; P.hCtu = (h + 63) / 64;
-  P.stride[0] = P.wCtu * 64; P.stride[1] = P.stride[2] = P.wCtu * 32;
+  Params P; hostsim_params(P, w, h, bd, argc > 6 ? atoi(argv[6]) : 0);
   const int nctu = P.wCtu * P.hCtu;
-  Tables *tab = new Tables; hm355_build_tables(tab); P.tab = tab;
-  P.ws = (WorkSpace *)calloc(1, sizeof(WorkSpace));
   std::map<int, FinalPic> finals;
   const size_t frameBytes = (size_t)w * h * 3 / 2 * (bd == 8 ? 1 : 2);
   int bad = 0, nP = 0, nB = 0;
@@ -129,20 +120,9 @@ int main(int argc, char **argv)
     lastIp.sliceType = sliceType; lastIp.numRefIdx[0] = numRef[0]; lastIp.numRefIdx[1] = numRef[1]; lastIp.mvdL1Zero = misc[3]; lastIp.maxMergeCand = misc[4]; lastIp.cabacInitType = misc[6];
     if (sliceType != HM_P_SLICE && sliceType != HM_B_SLICE) continue;
     nP++;
-    FrameBuf fb; memset(&fb, 0, sizeof(fb));
+    FrameBuf fb; hostsim_alloc_frame(fb, P);
     fseek(fy, (long)(frameBytes * poc), SEEK_SET);
-    for (int c = 0; c < 3; c++) {
-      const size_t sz = (size_t)P.stride[c] * P.hCtu * (c ? 32 : 64);
-      fb.org[c] = (Pel *)calloc(sz, sizeof(Pel)); fb.rec[c] = (Pel *)calloc(sz, sizeof(Pel));
-      const int pw = w >> (c ? 1 : 0), ph = h >> (c ? 1 : 0);
-      for (int y = 0; y < ph; y++) for (int x = 0; x < pw; x++) {
-        unsigned v;
-        if (bd == 8) { unsigned char t; if (fread(&t, 1, 1, fy) != 1) return 3; v = t; } else { unsigned short t; if (fread(&t, 2, 1, fy) != 1) return 3; v = t; }
-        fb.org[c][y * P.stride[c] + x] = (Pel)v;
-      }
-    }
-    fb.meta = (CtuMeta *)calloc(nctu, sizeof(CtuMeta)); fb.coef = (TCoeff *)calloc((size_t)nctu * HM_COEF_CTU, sizeof(TCoeff));
-    fb.stat = (CtuStat *)calloc(nctu, sizeof(CtuStat)); fb.endState = (Cabac *)calloc(nctu, sizeof(Cabac));
+    if (!hostsim_read_yuv(fy, fb, P)) return 3;
     fb.imeta = (InterMeta *)calloc(nctu, sizeof(InterMeta)); fb.intMv = (MvD *)calloc((size_t)nctu * 32, sizeof(MvD));
     InterPic *ip = (InterPic *)calloc(1, sizeof(InterPic)); fb.ip = ip;
     ip->sliceType = sliceType; ip->poc = poc; ip->numRefIdx[0] = numRef[0]; ip->numRefIdx[1] = numRef[1];

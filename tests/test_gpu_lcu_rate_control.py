@@ -151,9 +151,7 @@ def test_lcu_rate_control_row_starts_take_the_real_flag(hm):
     enc.deblock_run([(2, qp - 4, np.zeros((2, 16), np.int32))])
     ref = enc.ref_from_slot(0, 0, False)
     lam = 0.4624 * 2.0 ** ((qp - 12) / 3.0)
-    sp = dict(slice_type=1, qp=qp, chroma_weight=hm.intra_lambda(qp)[1], poc=1, cabac_init_type=1, num_ref_idx=(1, 0), ref_poc=np.zeros((2, 16), np.int32),
-              col_from_l0=1, col_ref_idx=0, tmvp=1, mvd_l1_zero=0, max_merge_cand=5, check_ldc=1,
-              lambda_motion_sad=int(np.floor(65536.0 * np.sqrt(lam))), lambda_motion_sse=int(np.floor(65536.0 * lam)), **{"lambda": lam})
+    sp = hm.inter_slice_params("P", qp, lam, 1, (1, 0), np.zeros((2, 16), np.int32))
     rng = np.random.default_rng(3)
     qps = (qp + rng.integers(-3, 4, n)).clip(0, 51).astype(np.int8)
     lams = lam * 2.0 ** ((qps.astype(np.float64) - qp) / 3.0)

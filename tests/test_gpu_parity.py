@@ -95,7 +95,6 @@ def test_hip_p_slice_batch_equals_single(hm):
 def test_hip_inter_matches_oracle_on_fresh_inputs(built, hm, w, h, bd, wpp, kind):
     """P / B slices on freshly seeded pictures (no fixture): reference pictures = the HIP path's own I-slice reconstructions, two pictures
     per list; the HIP result must equal the oracle's bit for bit (decisions, motion, coefficients, costs, reconstruction)."""
-    import math
     import oracle
     qp, seed = 30, 77
     enc = hm.Encoder(w, h, bd, wpp, max_batch=2)
@@ -111,13 +110,11 @@ def test_hip_inter_matches_oracle_on_fresh_inputs(built, hm, w, h, bd, wpp, kind
     if kind == "B":
         ref_poc[1, :2] = (4, 0)
     lam = 0.4624 * 2.0 ** ((qp + 2 - 12) / 3.0) * 2.0
-    srec = {"poc": 2, "slice_type": 1 if kind == "P" else 0, "qp": qp + 2, "lambda": lam, "weight_cb": hm.intra_lambda(qp + 2)[1],
-            "cabac_init_type": 1 if kind == "P" else 0, "num_ref_idx": (2, 0 if kind == "P" else 2), "ref_poc": ref_poc, "col_from_l0": 0 if kind == "B" else 1,
-            "col_ref_idx": 0, "tmvp": 1, "mvd_l1_zero": 0, "max_merge_cand": 5, "check_ldc": 0 if kind == "B" else 1,
-            "lambda_motion_sad": int(math.floor(65536.0 * math.sqrt(lam))), "lambda_motion_sse": int(math.floor(65536.0 * lam))}
+    sp = hm.inter_slice_params(kind, qp + 2, lam, 2, (2, 0 if kind == "P" else 2), ref_poc, col_from_l0=0 if kind == "B" else 1, check_ldc=0 if kind == "B" else 1)
+    srec = dict(sp, weight_cb=sp["chroma_weight"])           # as an 'S' record, for the oracle and ldp_slice_inputs
     cur = synth.frame(w, h, bd, 2, seed)
     want_rec, want_ctus, want_ictus = oracle.compress_inter(cur, bd, srec, finals, wpp=wpp)
-    sp, refs = common.ldp_slice_inputs(srec, finals)
+    _, refs = common.ldp_slice_inputs(srec, finals)
     rec, ctus, ictus, _ = enc.compress_inter(cur, sp, refs)
     enc.close()
     for f in ("total_bits", "total_dist", "total_cost", "depth", "part_size", "pred_mode", "tr_idx", "cbf", "tskip", "coeff_y", "coeff_cb", "coeff_cr"):
@@ -329,10 +326,7 @@ def test_full_size_pictures_match_reference_digests(hm, name):
             rec, ctus, _ = enc.download(0)
             dig = common.ctu_digests(ctus)
         else:
-            sp = {k: p[k] for k in ("slice_type", "qp", "lambda", "poc", "cabac_init_type", "num_ref_idx", "ref_poc", "col_from_l0", "col_ref_idx", "tmvp",
-                                    "mvd_l1_zero", "max_merge_cand", "check_ldc", "lambda_motion_sad", "lambda_motion_sse")}
-            sp["chroma_weight"] = p["weight_cb"]
-            refs = {int(q): dev_refs[int(q)] for l in range(2) for q in p["ref_poc"][l][:p["num_ref_idx"][l]]}
+            sp, refs = common.ldp_slice_inputs(p, None, {int(q): dev_refs[int(q)] for l in range(2) for q in p["ref_poc"][l][:p["num_ref_idx"][l]]})
             rec, ctus, ictus, _ = enc.compress_inter(planes, sp, refs)
             dig = common.ctu_digests(ctus, ictus)
         assert np.array_equal(dig, p["ctu_sha1"]), f"{what}: {_first_bad(dig, p['ctu_sha1'])} of {len(dig)}"
@@ -670,7 +664,6 @@ def test_full_size_inter_properties(built, hm, kind, w, h, bd, nref):
     not need the oracle at that size: (1) the same job in two batch slots gives identical results; (2) picture totals are the sums of
     the per-CTU totals; (3) crop invariance: the four top-left CTUs only read the picture and the reference pictures inside the top-left
     384x256 region (search range 64 + interpolation taps), so they equal the oracle's result on that crop with the cropped references."""
-    import math
     import oracle
     qp, seed, cw, ch = 32, 4321, 384, 256
     enc = hm.Encoder(w, h, bd, 1, max_batch=2)
@@ -697,12 +690,10 @@ def test_full_size_inter_properties(built, hm, kind, w, h, bd, nref):
         ref_poc[1, :len(pocs)] = pocs[::-1]
     qps = qp + (3 if kind == "P" else 2)
     lam = (0.4624 if kind == "P" else 0.3536) * 2.0 ** ((qps - 12) / 3.0) * min(4.0, max(2.0, (qps - 12) / 6.0))
-    srec = {"poc": cur_poc, "slice_type": 1 if kind == "P" else 0, "qp": qps, "lambda": lam, "weight_cb": hm.intra_lambda(qps)[1],
-            "cabac_init_type": 1 if kind == "P" else 0, "num_ref_idx": (len(pocs), 0 if kind == "P" else len(pocs)), "ref_poc": ref_poc, "col_from_l0": 1,
-            "col_ref_idx": 0, "tmvp": 1, "mvd_l1_zero": 0, "max_merge_cand": 5, "check_ldc": 1 if kind == "P" else 0,
-            "lambda_motion_sad": int(math.floor(65536.0 * math.sqrt(lam))), "lambda_motion_sse": int(math.floor(65536.0 * lam))}
+    sp = hm.inter_slice_params(kind, qps, lam, cur_poc, (len(pocs), 0 if kind == "P" else len(pocs)), ref_poc, check_ldc=1 if kind == "P" else 0)
+    srec = dict(sp, weight_cb=sp["chroma_weight"])           # as an 'S' record, for the oracle and ldp_slice_inputs
     cur = synth.frame(w, h, bd, cur_poc, seed)
-    sp, refs = common.ldp_slice_inputs(srec, finals)
+    _, refs = common.ldp_slice_inputs(srec, finals)
     (rec0, ctus0, ictus0, st0), (rec1, ctus1, ictus1, st1) = enc.compress_inter_batch([(cur, sp, refs), (cur, sp, refs)])
     enc.close()
     for f in ctus0.dtype.names:

@@ -87,10 +87,8 @@ def test_hostsim_of_kernel_source_matches_reference_fixture(tmp_path):
     yuv = tmp_path / "in.yuv"
     synth.write_yuv(str(yuv), cfg["width"], cfg["height"], cfg["bit_depth"], cfg["frames"], cfg["seed"])
     import gen_golden
-    for flag, exe in (("", "hostsim"), ("-DHM355_HOSTSIM_REVERSE", "hostsim_rev")):
-        out = tmp_path / exe
-        cmd = ["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-w"] + ([flag] if flag else []) + ["-o", str(out), os.path.join(ROOT, "tests", "hostsim", "hostsim.cpp")]
-        subprocess.run(cmd, check=True)
+    for flags, exe in ((), "hostsim"), (("-DHM355_HOSTSIM_REVERSE",), "hostsim_rev"):
+        out = common.build_hostsim(tmp_path, "hostsim", *flags, exe=exe)
         dump = tmp_path / (exe + ".bin")
         subprocess.run([str(out), str(yuv), str(cfg["width"]), str(cfg["height"]), str(cfg["bit_depth"]), str(cfg["frames"]),
                         str(cfg["qp"]), str(cfg["wpp"]), str(dump)], check=True)
@@ -105,8 +103,7 @@ def test_hostsim_result_does_not_depend_on_what_the_buffers_held(tmp_path):
     coefficient / statistics arrays and CABAC hand-off states filled with noise (HM355_DIRTY, three seeds) gives the result of the zero-filled run."""
     import filecmp
     import synth
-    out = tmp_path / "hostsim"
-    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-w", "-o", str(out), os.path.join(ROOT, "tests", "hostsim", "hostsim.cpp")], check=True)
+    out = common.build_hostsim(tmp_path, "hostsim")
     for (w, h, bd, qp, wpp, seed) in [(192, 128, 10, 30, 1, 31), (200, 136, 8, 22, 0, 9)]:
         yuv = tmp_path / f"in_{w}.yuv"
         synth.write_yuv(str(yuv), w, h, bd, 2, seed)
@@ -126,8 +123,7 @@ def test_hostsim_of_kernel_source_matches_oracle_at_extreme_qps(tmp_path):
     with and without WPP: the code paths behind the early terminations of the CU / residual quadtrees and the LDS-resident RDOQ state
     of 32x32 blocks, against the oracle on fresh inputs."""
     import synth, gen_golden, oracle
-    out = tmp_path / "hostsim"
-    subprocess.run(["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-w", "-o", str(out), os.path.join(ROOT, "tests", "hostsim", "hostsim.cpp")], check=True)
+    out = common.build_hostsim(tmp_path, "hostsim")
     for (w, h, bd, qp, wpp, seed) in [(320, 192, 10, 12, 1, 21), (256, 136, 8, 47, 0, 22), (384, 192, 10, 22, 1, 23), (200, 192, 8, 3, 0, 24)]:
         yuv = tmp_path / f"in{seed}.yuv"
         synth.write_yuv(str(yuv), w, h, bd, 1, seed)
@@ -151,10 +147,8 @@ def test_hostsim_of_kernel_source_matches_reference_p_slices(tmp_path, name):
     yuv, dump = tmp_path / "in.yuv", tmp_path / "dump2.bin"
     synth.write_yuv(str(yuv), cfg["width"], cfg["height"], cfg["bit_depth"], cfg["frames"], cfg["seed"])
     hmd2.write(str(dump), recs, bits=True)
-    for flag, exe in (("", "hostsim_inter"), ("-DHM355_HOSTSIM_REVERSE", "hostsim_inter_rev")):
-        out = tmp_path / exe
-        cmd = ["g++", "-O2", "-std=c++14", "-ffp-contract=off", "-w"] + ([flag] if flag else []) + ["-o", str(out), os.path.join(ROOT, "tests", "hostsim", "hostsim_inter.cpp")]
-        subprocess.run(cmd, check=True)
+    for flags, exe in ((), "hostsim_inter"), (("-DHM355_HOSTSIM_REVERSE",), "hostsim_inter_rev"):
+        out = common.build_hostsim(tmp_path, "hostsim_inter", *flags, exe=exe)
         r = subprocess.run([str(out), str(yuv), str(dump), str(cfg["width"]), str(cfg["height"]), str(cfg["bit_depth"]), str(cfg["wpp"])],
                            capture_output=True, text=True)
         assert r.returncode == 0 and "all bit-exact" in r.stdout, r.stdout[-2000:]

@@ -1,12 +1,10 @@
 """Rehearsal of the row-band pipeline with REAL ranks: `python -m torch.distributed.run --nproc-per-node 2 tools/bands_two_ranks.py`
 starts two processes that share one GPU (gloo transport; RCCL needs one GPU per rank), each searching its band of CTU rows of the
 same pictures through hm-16.2_amd/bands.py; rank 0 then gathers the bands and compares them with an unsplit run."""
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "hm-16.2_amd")]
+import _paths
 import numpy as np
 import torch
 import torch.distributed as dist

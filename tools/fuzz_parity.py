@@ -1,9 +1,8 @@
 """Diagnostic: randomized parity sweep HIP vs oracle (sizes, bit depths, QPs, WPP, slice types, reference counts).
 usage: fuzz_parity.py <cases> [seed]      (needs a GPU; the oracle runs on one host core)"""
-import math, os, sys, time
+import sys, time
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "hm-16.2_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
+import _paths
 import hm355, oracle, synth, common
 cases, seed0 = int(sys.argv[1]), int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed0)
@@ -41,14 +40,13 @@ for k in range(cases):
             ldc = int(all(p < cur_poc for p in l0 + (l1 if kind == "B" else [])))
             mvd0 = int(kind == "B" and rng.integers(0, 2) == 1 and ldc)
             lam = 0.4624 * 2.0 ** ((qp - 12) / 3.0) * 2.0
-            srec = {"poc": cur_poc, "slice_type": 1 if kind == "P" else 0, "qp": qp, "lambda": lam, "weight_cb": hm355.intra_lambda(qp)[1],
-                    "cabac_init_type": int(rng.integers(0, 2)), "num_ref_idx": (len(l0), len(l1) if kind == "B" else 0), "ref_poc": ref_poc,
-                    "col_from_l0": int(rng.integers(0, 2)) if kind == "B" else 1, "col_ref_idx": 0, "tmvp": int(rng.integers(0, 2)), "mvd_l1_zero": mvd0,
-                    "max_merge_cand": int(rng.integers(1, 6)), "check_ldc": ldc,
-                    "lambda_motion_sad": int(math.floor(65536.0 * math.sqrt(lam))), "lambda_motion_sse": int(math.floor(65536.0 * lam))}
+            sp = hm355.inter_slice_params(kind, qp, lam, cur_poc, (len(l0), len(l1) if kind == "B" else 0), ref_poc,       # the draws in this order: a seed names a case
+                                          cabac_init_type=int(rng.integers(0, 2)), col_from_l0=int(rng.integers(0, 2)) if kind == "B" else 1,
+                                          tmvp=int(rng.integers(0, 2)), mvd_l1_zero=mvd0, max_merge_cand=int(rng.integers(1, 6)), check_ldc=ldc)
+            srec = dict(sp, weight_cb=sp["chroma_weight"])           # as an 'S' record, for the oracle and ldp_slice_inputs
             cur = synth.frame(w, h, bd, cur_poc, seed)
             want_rec, want_ctus, want_ictus = oracle.compress_inter(cur, bd, srec, finals, wpp=wpp)
-            sp, refs = common.ldp_slice_inputs(srec, finals)
+            _, refs = common.ldp_slice_inputs(srec, finals)
             rec, ctus, ictus, _ = enc.compress_inter(cur, sp, refs)
             for f in ("total_bits", "total_dist", "total_cost", "depth", "part_size", "pred_mode", "tr_idx", "cbf", "tskip", "coeff_y", "coeff_cb", "coeff_cr"):
                 assert np.array_equal(ctus[f], want_ctus[f]), f

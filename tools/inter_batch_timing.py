@@ -1,9 +1,8 @@
 """Diagnostic: P-slice throughput with n independent 1080p streams in one call (config 3 shape: low-delay P, 8-bit).
 usage: inter_batch_timing.py <w> <h> <wpp> <streams> [nref]"""
-import math, os, sys, time
+import sys, time
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "hm-16.2_amd")]
+import _paths
 import hm355, synth
 w, h, wpp, S = (int(v) for v in sys.argv[1:5])
 nref = int(sys.argv[5]) if len(sys.argv) > 5 else 4
@@ -13,10 +12,7 @@ n = enc.num_ctus
 jobs = []
 lam = 0.4624 * 2.0 ** ((qp + 3 - 12) / 3.0) * min(4.0, max(2.0, (qp + 3 - 12) / 6.0))
 ref_poc = np.zeros((2, 16), np.int32); ref_poc[0, :nref] = list(range(nref - 1, -1, -1))
-sp = dict(qp=qp + 3, chroma_weight=hm355.intra_lambda(qp + 3)[1], poc=nref, cabac_init_type=1, num_ref_idx=(nref, 0), ref_poc=ref_poc,
-          col_from_l0=1, col_ref_idx=0, tmvp=1, mvd_l1_zero=0, max_merge_cand=5, check_ldc=1,
-          lambda_motion_sad=int(math.floor(65536.0 * math.sqrt(lam))), lambda_motion_sse=int(math.floor(65536.0 * lam)))
-sp["lambda"] = lam
+sp = hm355.inter_slice_params("P", qp + 3, lam, nref, (nref, 0), ref_poc)
 t0 = time.time()
 for s in range(S):
     frames = [synth.frame(w, h, bd, i, 100 + s) for i in range(nref + 1)]

@@ -10,25 +10,17 @@ slots called in turn (kernel time from HIP events, luma bytes read over kernel t
 import argparse
 import ctypes as C
 import json
-import math
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "hm-16.2_amd")]
-import hm355  # noqa: E402
-import synth  # noqa: E402
+import _paths
+import hm355
+import synth
 
 
 def p_slice(qp):
-    lam = 0.4624 * 2.0 ** ((qp - 12) / 3.0)
-    ref_poc = np.zeros((2, 16), np.int32)
-    return dict(slice_type=1, qp=qp, chroma_weight=hm355.intra_lambda(qp)[1], poc=1, cabac_init_type=1, num_ref_idx=(1, 0), ref_poc=ref_poc,
-                col_from_l0=1, col_ref_idx=0, tmvp=1, mvd_l1_zero=0, max_merge_cand=5, check_ldc=1,
-                lambda_motion_sad=int(math.floor(65536.0 * math.sqrt(lam))), lambda_motion_sse=int(math.floor(65536.0 * lam)), **{"lambda": lam})
+    return hm355.inter_slice_params("P", qp, 0.4624 * 2.0 ** ((qp - 12) / 3.0), 1, (1, 0), np.zeros((2, 16), np.int32))
 
 
 def p_streams(n, w=1920, h=1080, qp=32, seed=5):

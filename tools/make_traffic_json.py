@@ -2,7 +2,7 @@
 `python3 bench.py --steps S --warmup W --no-cpu-baseline`.  The record carries the build id of the library that ran, so bench.py quotes it only for that build.
 usage: make_traffic_json.py <fetch_dir> <write_dir> <out.json> <frames> <lanes> <kernel> [width height]"""
 import csv, glob, json, os, sys
-sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hm-16.2_amd")]
+import _paths
 import hm355
 
 

@@ -1,8 +1,8 @@
 """Diagnostic: the drop-in entry with host buffers in and out (hm355_compress_slices through Encoder.compress: upload, search, download of every
 picture's reconstruction / decisions / coefficients) on a batch of 4K pictures -- the PCIe-inclusive rate quoted in DESIGN section 7 (never bench.py's value).
 usage: pcie_inclusive.py [pictures=192]"""
-import json, os, sys, time
-sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hm-16.2_amd')]
+import json, sys, time
+import _paths
 import hm355, synth
 F = int(sys.argv[1]) if len(sys.argv) > 1 else 192
 w, h, bd = 3840, 2160, 10

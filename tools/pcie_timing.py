@@ -1,7 +1,7 @@
 """Host<->device transfer cost of the boundary (hm355_upload / hm355_download) per 4K picture, to quote the
 PCIe-inclusive rate next to the HBM-resident rate bench.py reports."""
-import os, sys, time
-sys.path[:0] = [os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hm-16.2_amd')]
+import time
+import _paths
 import hm355, synth
 w, h, bd, F = 3840, 2160, 10, 8
 enc = hm355.Encoder(w, h, bd, 1, F)

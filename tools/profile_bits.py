@@ -1,7 +1,7 @@
 """Diagnostic: cycle shares inside the bitstream pass (needs tools/libhm355_prof.so built with -DHM355_PROFILE).
 usage: profile_bits.py <lib> <w> <h> <pictures>"""
 import ctypes as C, sys, numpy as np
-sys.path[:0] = ['hm-16.2_amd']
+import _paths
 import hm355, synth
 lib = hm355.load_library(sys.argv[1])
 w, h, F = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])

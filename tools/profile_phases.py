@@ -1,6 +1,6 @@
 """Diagnostic: per-phase cycle shares of the CTU kernel (needs gpurun_out/libhm355_prof.so built with -DHM355_PROFILE)."""
 import ctypes as C, sys, time, numpy as np
-sys.path[:0] = ['hm-16.2_amd']
+import _paths
 import hm355, synth
 lib = hm355.load_library(sys.argv[1])
 w, h, F = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])

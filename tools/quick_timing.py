@@ -1,6 +1,6 @@
 """Diagnostic: time of one search step over F copies of a picture.  usage: quick_timing.py <w> <h> <F> [lib.so]  (a second library for A/B runs on the same box)"""
 import sys, time, numpy as np
-import os; sys.path[:0]=[os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),'hm-16.2_amd')]
+import os, _paths
 import hm355, synth
 w,h,bd,F=int(sys.argv[1]),int(sys.argv[2]),10,int(sys.argv[3])
 lib=hm355.load_library(sys.argv[4]) if len(sys.argv)>4 else None

@@ -4,8 +4,7 @@ import ctypes as C
 import os
 import sys
 import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "hm-16.2_amd"), os.path.join(ROOT, "tests")]
+from _paths import ROOT
 import common, hm355, synth
 lib = hm355.load_library(os.path.join(ROOT, "tools", "libhm355_trace.so"))
 lib.hm355_read_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong]
