@@ -18,6 +18,7 @@
 #include "hm355_sao.h"
 #include "hm355_bits_kernel.h"
 #include "hm355_ingest.h"
+#include "hm355_picstat.h"
 #include "hm355_host_common.h"
 #include "../../include/hm355.h"
 
@@ -284,6 +285,7 @@ struct hm355_ctx {
   DevBuf<BitsParams> dBits;    // [max_batch] bitstream pass parameters / results
   DevBuf<IngestParams> dIngest; // [max_batch] ingest / output parameters
   DevBuf<int32_t> dIntraCost;  // [numCtus] hm355_intra_cost
+  DevBuf<PicStatParams> dPicStat; DevBuf<PicStatAcc> dPicAcc;   // [max_batch] picture statistics: parameters / accumulators
 };
 
 #define HM_CHECK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HM355_ERR_DEVICE; } } while (0)
@@ -1407,6 +1409,79 @@ extern "C" int hm355_download_file_frames(hm355_ctx *c, int n, void *const *fram
   if (rc != HM355_OK) return rc;
   for (int f = 0; f < n; f++) HM_CHECK(c, hipMemcpy(frames[f], c->slots[f].rawOut, bytes, hipMemcpyDeviceToHost));
   return HM355_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// picture statistics (TEncGOP::xCalculateAddPSNR, the decoded picture hash) on the pictures of the slots
+// ------------------------------------------------------------------------------------------------
+extern "C" int hm355_picture_stats_run(hm355_ctx *c, int n, hm355_picstat_desc *descs)
+{
+  if (!c || !descs || n < 1 || n > (int)c->slots.size()) return HM355_ERR_ARG;
+  const Params &P = c->hp;
+  std::vector<FrameBuf> fbs(n); std::vector<PicStatParams> pps(n);
+  int anyCrc = 0, anyMd5 = 0;
+  for (int f = 0; f < n; f++) {
+    const hm355_picstat_desc &d = descs[f];
+    if (d.hash_method < 0 || d.hash_method > 3) return fail(c, HM355_ERR_ARG, "hm355_picture_stats_run: hash_method must be 0 (none), 1 (MD5), 2 (CRC) or 3 (checksum)");
+    if (d.pad_right < 0 || d.pad_bottom < 0 || (d.pad_right & 1) || (d.pad_bottom & 1) || d.pad_right >= P.width || d.pad_bottom >= P.height)
+      return fail(c, HM355_ERR_ARG, "hm355_picture_stats_run: the pads must be even, not negative and smaller than the picture");
+    fbs[f] = c->slots[f].fb;
+    pps[f].hashMethod = d.hash_method; pps[f].padRight = d.pad_right; pps[f].padBottom = d.pad_bottom; pps[f].pad = 0;
+    anyMd5 |= d.hash_method == 1; anyCrc |= d.hash_method == 2;
+  }
+  HM_CHECK(c, c->dPicAcc.ensure(c->slots.size()));
+  int rc = stage_slots(c, fbs, c->dPicStat, pps);
+  if (rc != HM355_OK) return rc;
+  const Params *dP = c->lane[0].dP; const PicStatParams *dPp = c->dPicStat; PicStatAcc *dAcc = c->dPicAcc;
+  const int groups = ((P.width + 7) / 8) * P.height, chunks = ps_crc_chunks_per_row(P.width, HM_CRC_CHUNK) * P.height;
+  rc = timed_launches(c, 1 + anyCrc + anyMd5, [&](hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(dAcc, 0, sizeof(PicStatAcc) * n, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hm355_picstat_kernel, dim3((groups + HM_PS_BLOCK * HM_PS_GROUPS - 1) / (HM_PS_BLOCK * HM_PS_GROUPS), 1, 3 * n), dim3(HM_PS_BLOCK), 0, s, dP, dPp, dAcc);
+    if (anyCrc) hipLaunchKernelGGL(hm355_crc_kernel, dim3((chunks + HM_PS_BLOCK - 1) / HM_PS_BLOCK, 1, 3 * n), dim3(HM_PS_BLOCK), 0, s, dP, dPp, dAcc, HM_CRC_CHUNK);
+    if (anyMd5) hipLaunchKernelGGL(hm355_md5_kernel, dim3((n + 63) / 64, 3, 1), dim3(64), 0, s, dP, dPp, dAcc, n);
+    return hipGetLastError();
+  });
+  if (rc != HM355_OK) return rc;
+  std::vector<PicStatAcc> acc(n);
+  HM_CHECK(c, hipMemcpy(acc.data(), c->dPicAcc, sizeof(PicStatAcc) * n, hipMemcpyDeviceToHost));
+  const int bps = P.bitDepth > 8 ? 2 : 1;
+  for (int f = 0; f < n; f++) {
+    hm355_picstat_desc &d = descs[f];
+    memset(d.digest, 0, sizeof(d.digest));
+    d.digest_len = d.hash_method == 1 ? 16 : (d.hash_method == 2 ? 2 : (d.hash_method == 3 ? 4 : 0));
+    for (int k = 0; k < 3; k++) {
+      const int cs = k ? 1 : 0, wc = P.width >> cs, hc = P.height >> cs;
+      const int size = (wc - (d.pad_right >> cs)) * (hc - (d.pad_bottom >> cs));
+      d.ssd[k] = acc[f].ssd[k];
+      d.psnr[k] = ps_psnr(acc[f].ssd[k], size, P.bitDepth);       // the reference's expressions and libm call
+      d.mse[k] = ps_mse(acc[f].ssd[k], size);
+      if (d.hash_method == 1) for (int i = 0; i < 16; i++) d.digest[k][i] = (uint8_t)(acc[f].md5[k][i >> 2] >> (8 * (i & 3)));
+      else if (d.hash_method == 2) { const uint32_t v = acc[f].crc[k] ^ ps_crc_init_term(wc, hc, bps); d.digest[k][0] = (uint8_t)(v >> 8); d.digest[k][1] = (uint8_t)v; }
+      else if (d.hash_method == 3) for (int i = 0; i < 4; i++) d.digest[k][i] = (uint8_t)(acc[f].cksum[k] >> (24 - 8 * i));
+    }
+  }
+  return HM355_OK;
+}
+
+extern "C" int hm355_upload_rec(hm355_ctx *c, int slot, const hm355_planes *rec)
+{
+  if (!c || !rec || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  for (int k = 0; k < 3; k++) if (!rec->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
+  HM_CHECK(c, copy_planes(c, c->slots[slot].fb.rec, rec->plane, hipMemcpyHostToDevice, false));
+  return HM355_OK;
+}
+
+// host buffers in: the two pictures go to slot 0 first
+extern "C" int hm355_picture_stats(hm355_ctx *c, hm355_picstat_desc *desc, const hm355_planes *org, const hm355_planes *rec)
+{
+  if (!c || !desc || !org || !rec) return HM355_ERR_ARG;
+  for (int k = 0; k < 3; k++) if (!org->plane[k] || !rec->plane[k]) return fail(c, HM355_ERR_ARG, "null plane");
+  Slot &sl = c->slots[0];
+  HM_CHECK(c, copy_planes(c, sl.fb.org, org->plane, hipMemcpyHostToDevice, false));
+  HM_CHECK(c, copy_planes(c, sl.fb.rec, rec->plane, hipMemcpyHostToDevice, false));
+  sl.ctusDone = 0;                  // a new picture
+  return hm355_picture_stats_run(c, 1, desc);
 }
 
 // ------------------------------------------------------------------------------------------------

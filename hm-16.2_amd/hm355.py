@@ -89,7 +89,26 @@ class BitsDesc(C.Structure):
                 ("next_cabac_init_type", C.c_int32), ("num_bins", C.c_uint32)]
 
 
-EXPORTS = ["hm355_build_id", "hm355_set_dqp", "hm355_get_dqp", "hm355_preanalyze", "hm355_set_ctu_rc", "hm355_slice_begin", "hm355_slice_begin_inter",
+class PicStatDesc(C.Structure):
+    """hm355_picstat_desc: SSD / PSNR / MSE per component and the decoded picture hash of one picture"""
+    _fields_ = [("hash_method", C.c_int32), ("pad_right", C.c_int32), ("pad_bottom", C.c_int32), ("ssd", C.c_uint64 * 3),
+                ("psnr", C.c_double * 3), ("mse", C.c_double * 3), ("digest", (C.c_uint8 * 16) * 3), ("digest_len", C.c_int32)]
+
+
+HASH_NAMES = {1: "MD5", 2: "CRC", 3: "Checksum"}       # the tag of the reference's log line (TEncGOP.cpp:1789-1802)
+
+
+def digest_to_string(digest, digest_len):
+    """what digestToString (TComPicYuvMD5.cpp:207) prints: the components' digests in hex, separated by commas"""
+    return ",".join(bytes(bytearray(d[:digest_len])).hex() for d in digest) if digest_len else ""
+
+
+def psnr_string(psnr):
+    """the picture-dependent piece of the reference's log line (TEncGOP.cpp:2350)"""
+    return " [Y %6.4f dB    U %6.4f dB    V %6.4f dB]" % tuple(psnr)
+
+
+EXPORTS = ["hm355_build_id", "hm355_picture_stats_run", "hm355_picture_stats", "hm355_upload_rec", "hm355_set_dqp", "hm355_get_dqp", "hm355_preanalyze", "hm355_set_ctu_rc", "hm355_slice_begin", "hm355_slice_begin_inter",
            "hm355_run_ctus", "hm355_ctu_rc_feedback", "hm355_download_inter", "hm355_slice_end", "hm355_intra_cost","hm355_create", "hm355_destroy", "hm355_last_error", "hm355_compress_slice", "hm355_compress_slices",
            "hm355_compress_slice_inter", "hm355_compress_slices_inter", "hm355_deblock", "hm355_deblock_run", "hm355_ref_from_slot", "hm355_ref_release", "hm355_ref_bytes", "hm355_ref_export", "hm355_ref_import", "hm355_sao_run",
            "hm355_num_substreams", "hm355_encode_slices_run", "hm355_encode_slice",
@@ -156,6 +175,9 @@ def load_library(path=LIB_PATH):
     lib.hm355_upload_file_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
     lib.hm355_download_file_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]
     lib.hm355_download_org.argtypes = [C.c_void_p, C.c_int, C.POINTER(Planes)]
+    lib.hm355_picture_stats_run.argtypes = [C.c_void_p, C.c_int, C.POINTER(PicStatDesc)]
+    lib.hm355_upload_rec.argtypes = [C.c_void_p, C.c_int, C.POINTER(Planes)]
+    lib.hm355_picture_stats.argtypes = [C.c_void_p, C.POINTER(PicStatDesc), C.POINTER(Planes), C.POINTER(Planes)]
     lib.hm355_num_substreams.argtypes = [C.c_void_p]
     lib.hm355_encode_slices_run.argtypes = [C.c_void_p, C.c_int, C.POINTER(BitsDesc)]
     lib.hm355_encode_slice.argtypes = [C.c_void_p, C.POINTER(BitsDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -578,6 +600,38 @@ class Encoder:
         p = _planes(planes)
         self._check(self.lib.hm355_download_org(self.h_, slot, C.byref(p)), "hm355_download_org")
         return planes
+
+    @staticmethod
+    def _picstat_result(d):
+        n = int(d.digest_len)
+        digest = [bytes(bytearray(d.digest[k])[:n]) for k in range(3)]
+        return dict(ssd=tuple(int(v) for v in d.ssd), psnr=tuple(float(v) for v in d.psnr), mse=tuple(float(v) for v in d.mse), digest=digest,
+                    digest_len=n, digest_string=digest_to_string(digest, n), psnr_string=psnr_string(d.psnr))
+
+    def picture_stats_run(self, descs):
+        """hm355_picture_stats_run on slots 0..n-1 (originals and reconstruction resident).  descs: dicts with hash_method (0 none, 1 MD5, 2 CRC,
+        3 checksum), pad_right, pad_bottom (luma samples, default 0).  Returns one dict per picture: ssd, psnr, mse (3-tuples), digest (3 byte
+        strings), digest_len, digest_string (what digestToString prints), psnr_string (the log line's PSNR piece)."""
+        n = len(descs)
+        arr = (PicStatDesc * n)()
+        for k, d in enumerate(descs):
+            arr[k].hash_method, arr[k].pad_right, arr[k].pad_bottom = int(d.get("hash_method", 0)), int(d.get("pad_right", 0)), int(d.get("pad_bottom", 0))
+        self._check(self.lib.hm355_picture_stats_run(self.h_, n, arr), "hm355_picture_stats_run")
+        return [self._picstat_result(arr[k]) for k in range(n)]
+
+    def upload_rec(self, slot, planes):
+        """hm355_upload_rec: host planes -> the reconstruction of a slot"""
+        r = [np.ascontiguousarray(p, np.uint16) for p in planes]
+        p = _planes(r)
+        self._check(self.lib.hm355_upload_rec(self.h_, slot, C.byref(p)), "hm355_upload_rec")
+
+    def picture_stats(self, org, rec, hash_method=0, pad_right=0, pad_bottom=0):
+        """hm355_picture_stats: host buffers in (uses slot 0); one result dict as picture_stats_run returns them"""
+        o = [np.ascontiguousarray(p, np.uint16) for p in org]; r = [np.ascontiguousarray(p, np.uint16) for p in rec]
+        po, pr = _planes(o), _planes(r)
+        d = PicStatDesc(int(hash_method), int(pad_right), int(pad_bottom))
+        self._check(self.lib.hm355_picture_stats(self.h_, C.byref(d), C.byref(po), C.byref(pr)), "hm355_picture_stats")
+        return self._picstat_result(d)
 
     def _bits_descs(self, descs):
         n = len(descs)

@@ -141,7 +141,17 @@ Void TEncGOP::compressGOP(Int iPOCLast, Int iNumPicRcvd, std::list<TComPic *> &r
       pcPic->setDeviceRef(ref);
       for (auto p : rcListPic) if (p->getDeviceRef() && p->getPOC() < pocCurr - 24) { hm355_ref_release(ctx, p->getDeviceRef()); p->setDeviceRef(nullptr); }   // out of every reference picture set
     }
+    xCalculateAddPSNR(pcPic);                                                                           // :1665-1696 (hash), :1725 (PSNR)
   }
+}
+
+// The finished picture is still in device slot 0 next to its original: the SSD per component and the digest come back, nothing else crosses PCIe.
+Void TEncGOP::xCalculateAddPSNR(TComPic *pcPic)
+{
+  hm355_ctx *ctx = m_pcEncTop->getDeviceContext();
+  hm355_picstat_desc &d = pcPic->getPicStat(); memset(&d, 0, sizeof(d));
+  d.hash_method = m_pcEncTop->getDecodedPictureHashSEIEnabled(); d.pad_right = m_pcEncTop->getPad(0); d.pad_bottom = m_pcEncTop->getPad(1);
+  if (hm355_picture_stats_run(ctx, 1, &d) != HM355_OK) { fprintf(stderr, "TEncGOP::xCalculateAddPSNR: %s\n", hm355_last_error(ctx)); exit(EXIT_FAILURE); }
 }
 
 Void TEncGOP::xSetReferences(TComSlice *pcSlice, Int pocCurr, Int iGOPid, std::list<TComPic *> &rcListPic)

@@ -91,10 +91,12 @@ public:
   Void setReconMark(Bool b) { m_reconMark = b; } Bool getReconMark() const { return m_reconMark; }
   Void setTLayer(Int t) { m_tLayer = t; } Int getTLayer() const { return m_tLayer; }
   Void setDeviceRef(hm355_ref *r) { m_devRef = r; } hm355_ref *getDeviceRef() const { return m_devRef; }   // the finished picture as a device-resident reference
+  // what TEncGOP::xCalculateAddPSNR and the decoded picture hash left for the picture: SSD / PSNR / MSE per component and the digest
+  hm355_picstat_desc &getPicStat() { return m_picStat; }
   // TEncPic (TEncPic.h:100-112), layer 0 of the QP adaptation: one activity per CTU and their average (TEncPreanalyzer::xPreanalyze)
   std::vector<Double> &getAQActivities() { return m_aqAct; } Void setAvgActivity(Double d) { m_aqAvg = d; } Double getAvgActivity() const { return m_aqAvg; }
 private:
-  std::vector<Double> m_aqAct; Double m_aqAvg = 0;
+  std::vector<Double> m_aqAct; Double m_aqAvg = 0; hm355_picstat_desc m_picStat = {};
   TComPicYuv m_org, m_rec; TComSlice m_slice; std::vector<hm355_ctu_out> m_ctus; std::vector<TComOutputBitstream> m_substreams;
   std::vector<hm355_ctu_inter_out> m_ictus; Bool m_reconMark = false; hm355_ref *m_devRef = nullptr; Int m_tLayer = 0;
 };
@@ -119,6 +121,8 @@ public:
   Void setWaveFrontSynchro(Int v) { m_iWaveFrontSynchro = v; } Void setFramesToBeEncoded(Int v) { m_framesToBeEncoded = v; }
   Void setLoopFilterDisable(Bool b) { m_bLoopFilterDisable = b; } Bool getLoopFilterDisable() const { return m_bLoopFilterDisable; }
   Void setUseSAO(Bool b) { m_bUseSAO = b; } Bool getUseSAO() const { return m_bUseSAO; }
+  Void setDecodedPictureHashSEIEnabled(Int b) { m_decodedPictureHashSEIEnabled = b; } Int getDecodedPictureHashSEIEnabled() const { return m_decodedPictureHashSEIEnabled; }   // --SEIDecodedPictureHash: 0 off, 1 MD5, 2 CRC, 3 checksum
+  Int getPad(Int i) const { return m_aiPad[i]; }     // TEncCfg::m_aiPad: the driver feeds pictures of the coded size, so both are 0
   Int getSourceWidth() const { return m_iSourceWidth; } Int getSourceHeight() const { return m_iSourceHeight; }
   Int getQP() const { return m_iQP; } Int getGOPSize() const { return m_iGOPSize; } Int getIntraPeriod() const { return m_uiIntraPeriod; }
   Int getWaveFrontsynchro() const { return m_iWaveFrontSynchro; } Int getInternalBitDepth() const { return m_bitDepth; }
@@ -126,6 +130,7 @@ protected:
   Int m_iSourceWidth = 0, m_iSourceHeight = 0, m_bitDepth = 8, m_iQP = 32, m_uiIntraPeriod = 1, m_iGOPSize = 1, m_iWaveFrontSynchro = 0, m_framesToBeEncoded = 0;
   Bool m_bLoopFilterDisable = true, m_bUseSAO = false;      // the loop filters are opt-in here (the reference's cfg files switch both on)
   Bool m_bUseAdaptiveQP = false; Int m_iQPAdaptationRange = 6;
+  Int m_decodedPictureHashSEIEnabled = 0, m_aiPad[2] = { 0, 0 };
   GOPEntry m_GOPList[16]; Bool m_bUseHADME = true; UInt m_maxNumMergeCand = 5; Int m_TMVPModeId = 1;
 };
 
@@ -188,6 +193,8 @@ private:
   std::vector<TComPic *> m_codedPics;
   // reference picture set and lists of a P / B slice (TEncTop::selectReferencePictureSet, the extra sets TAppEncCfg::xCheckParameter builds for
   // the start of the sequence, TComSlice::setRefPicList): no list modification, no long-term pictures
+  // TEncGOP::xCalculateAddPSNR (TEncGOP.cpp:2244) and the decoded picture hash (:1665-1696) in one call on the device-resident picture
+  Void xCalculateAddPSNR(TComPic *pcPic);
   Void xSetReferences(TComSlice *pcSlice, Int pocCurr, Int iGOPid, std::list<TComPic *> &rcListPic);
   TEncTop *m_pcEncTop = nullptr; TEncSlice *m_pcSliceEncoder = nullptr; TComLoopFilter *m_pcLoopFilter = nullptr; TEncSampleAdaptiveOffset *m_pcSAO = nullptr;
 };

@@ -5,6 +5,9 @@
 //   ... <dump.bin> ldp | ldb | ra [aq[range]] : (aq: --AdaptiveQP=1) the GOP table of cfg/encoder_lowdelay_P_main.cfg / encoder_lowdelay_main.cfg / encoder_randomaccess_main10.cfg (IntraPeriod -1, GOPSize 4, P slices with up to 4 references, loop filters
 //   on); the dump is then a "HMD3" stream in coding order: per picture i32 poc, sliceType, qp, depth, cabacInitType, numRefIdx0, numRefIdx1, colFromL0, mvdL1Zero, refPoc[2][16]; f64 lambda;
 //   u32 numCtus; per CTU the record of tests/hmd2.py CTU_DT (cost, bits, dist, decision arrays, motion arrays, coefficients); the finished planes.
+//   ... hash=N as the last argument (N = 1 MD5, 2 CRC, 3 checksum: --SEIDecodedPictureHash) writes <dump.bin>.picstat: per picture in coding order one line with the
+//   two pieces of the reference's log line that depend on the picture, " [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB]" and " [MD5:...]" / " [CRC:...]" /
+//   " [Checksum:...]" (TEncGOP.cpp:2350, :1789-1802); the dump and the .bits file are what they are without it.
 // The slice data of every picture (TEncSlice::encodeSlice) goes to <dump.bin>.bits: per picture u32 numSubstreams, then per substream u32 size + bytes.
 #include "TEncTop.h"
 #include <stdio.h>
@@ -46,7 +49,19 @@ int main(int argc, char **argv)
       enc.setGOPEntry(i, e);
     }
   }
+  const int hashMethod = argc > 9 && !strncmp(argv[argc - 1], "hash=", 5) ? atoi(argv[argc - 1] + 5) : 0;
+  enc.setDecodedPictureHashSEIEnabled(hashMethod);
   enc.create(); enc.init();
+  FILE *fs = hashMethod ? fopen((std::string(argv[8]) + ".picstat").c_str(), "w") : NULL;
+  if (hashMethod && !fs) { perror("open"); return 1; }
+  auto logPicture = [&](TComPic *pic) {               // the picture-dependent pieces of the reference's "POC ..." line
+    if (!fs) return;
+    const hm355_picstat_desc &d = pic->getPicStat();
+    fprintf(fs, " [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB]", d.psnr[0], d.psnr[1], d.psnr[2]);
+    fprintf(fs, " [%s:", d.hash_method == 1 ? "MD5" : (d.hash_method == 2 ? "CRC" : "Checksum"));
+    for (int c = 0; c < 3; c++) { if (c) fputc(',', fs); for (int i = 0; i < d.digest_len; i++) fprintf(fs, "%02x", d.digest[c][i]); }
+    fprintf(fs, "]\n");
+  };
   FILE *fb = fopen((std::string(argv[8]) + ".bits").c_str(), "wb");
   if (!fb) { perror("open"); return 1; }
   fwrite(ldp ? "HMD3" : "HMD1", 1, 4, fo);
@@ -84,6 +99,7 @@ int main(int argc, char **argv)
         for (int c = 0; c < 3; c++) fwrite(pic->getPicYuvRec()->getAddr(ComponentID(c)), 2, (size_t)org.getWidth(ComponentID(c)) * org.getHeight(ComponentID(c)), fo);
         const uint32_t ns = (uint32_t)pic->getSubstreams().size(); fwrite(&ns, 4, 1, fb);
         for (uint32_t k = 0; k < ns; k++) { const std::vector<uint8_t> &b = pic->getSubstreams()[k].getFIFO(); const uint32_t nb = (uint32_t)b.size(); fwrite(&nb, 4, 1, fb); if (nb) fwrite(b.data(), 1, nb, fb); }
+        logPicture(pic);
       }
       continue;
     }
@@ -98,8 +114,10 @@ int main(int argc, char **argv)
     for (int c = 0; c < 3; c++) fwrite(pic->getPicYuvRec()->getAddr(ComponentID(c)), 2, (size_t)org.getWidth(ComponentID(c)) * org.getHeight(ComponentID(c)), fo);
     const uint32_t ns = (uint32_t)pic->getSubstreams().size(); fwrite(&ns, 4, 1, fb);
     for (uint32_t k = 0; k < ns; k++) { const std::vector<uint8_t> &b = pic->getSubstreams()[k].getFIFO(); const uint32_t nb = (uint32_t)b.size(); fwrite(&nb, 4, 1, fb); if (nb) fwrite(b.data(), 1, nb, fb); }
+    logPicture(pic);
   }
   enc.destroy();
+  if (fs) fclose(fs);
   fclose(fo); fclose(fi); fclose(fb);
   return 0;
 }

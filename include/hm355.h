@@ -198,6 +198,30 @@ int hm355_encode_slices_run(hm355_ctx *ctx, int n, hm355_bits_desc *descs);
  * hm355_sao_run returns them (NULL with sao_enabled 0).  Uses slot 0. */
 int hm355_encode_slice(hm355_ctx *ctx, hm355_bits_desc *desc, const hm355_ctu_out *ctus, const hm355_ctu_inter_out *ictus, const int32_t *sao);
 
+/* ---- picture statistics: what TEncGOP::compressGOP does with the finished picture -- TEncGOP::xCalculateAddPSNR (TEncGOP.cpp:2244-2368, called
+ * at :1725 for every picture) and the decoded picture hash of --SEIDecodedPictureHash (TEncGOP.cpp:1665-1696; TComPicYuvMD5.cpp calcMD5 / calcCRC /
+ * calcChecksum) -- on the device, so that only a few bytes per picture cross PCIe.  The SSD original - reconstruction runs per component over the
+ * picture without its right / bottom padding (TEncCfg::m_aiPad); the hash runs over the whole coded plane.  PSNR and MSE are the reference's double
+ * expressions (:2287-2290), evaluated on the host from the 64-bit SSD.  digest holds digest_len bytes per component in the order
+ * TComDigest::hash holds them (MD5: the 16 digest bytes; CRC: 2 bytes, high first; checksum: 4 bytes, high first); the SEI writer stays with
+ * the caller.  4:2:0; no colour-space-converted PSNR, no field PSNR. ---- */
+typedef struct {
+  int32_t hash_method;                 /* 0 none, 1 MD5, 2 CRC, 3 checksum (--SEIDecodedPictureHash) */
+  int32_t pad_right, pad_bottom;       /* luma samples of TEncCfg::m_aiPad[0] / [1] (even, smaller than the picture): excluded from SSD / PSNR, included in the hash */
+  uint64_t ssd[3];                     /* out */
+  double   psnr[3], mse[3];            /* out */
+  uint8_t  digest[3][16];              /* out: digest_len bytes per component */
+  int32_t  digest_len;                 /* out: 16 / 2 / 4, 0 with hash_method 0 */
+} hm355_picstat_desc;
+/* device-resident: slots 0..n-1, the reconstruction as it stands (after hm355_sao_run: the finished picture) against the slots' originals.
+ * Reads the slots only: nothing a later call sees is changed. */
+int hm355_picture_stats_run(hm355_ctx *ctx, int n, hm355_picstat_desc *descs);
+/* host buffers in (uses slot 0: its original and reconstruction planes are overwritten), the drop-in form next to hm355_deblock */
+int hm355_picture_stats(hm355_ctx *ctx, hm355_picstat_desc *desc, const hm355_planes *org, const hm355_planes *rec);
+/* host -> the reconstruction planes of a slot: a picture that was reconstructed elsewhere, next to hm355_upload for its original, so that
+ * hm355_picture_stats_run can take a batch of them */
+int hm355_upload_rec(hm355_ctx *ctx, int slot, const hm355_planes *rec);
+
 /* ---- picture ingest and output: TVideoIOYuv::read / ::write (TVideoIOYuv.cpp:633-792) for planar 4:2:0 files, as TAppEncTop::encode drives them
  * (:431 read into the padded source picture, :603 write of the reconstruction with the conformance window).  The frames travel as they are on
  * disk (8-bit samples, or 16-bit little endian when file_bit_depth > 8); bit-depth scaling, padding by repetition up to the configured
