@@ -260,7 +260,7 @@ struct Lane {           // one launch of the search in flight: its own stream, s
   DevBuf<WorkItem> dItems; // the work list, grown to the longest one so far
   DevBuf<unsigned int> dSched; // [0] ticket, [1] abort, [2] CTUs published by the launch (the spin timeout watches it); lane 0: [8] ticket, [9] abort of the bitstream launch
   std::vector<WorkItem> items; std::vector<int> stepStart; std::vector<FrameBuf> fbs;
-  long long key[5] = {}; int keyValid = 0, fewWaves = -1;   // fewWaves: the value dP holds (-1: dP not written yet)
+  long long key[5] = {}; int keyValid = 0, fewWaves = -1, fast = 0;   // fewWaves, fast: the values dP holds (-1: dP not written yet; fast = esd | cfm << 1 | ecu << 2)
   int busy = 0, grid = 0, inFixup = 0, prepared = 0;   // prepared: the launch ran on slots an open slice prepared (hm355_run_ctus)
   DevBuf<Pel> dTeamWin; size_t teamCap = 0;   // team launches (hm355_team.h): the helpers' reconstruction windows, for teamCap teams
   ~Lane() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (stream) (void)hipStreamDestroy(stream); }
@@ -506,6 +506,10 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   for (int f = 0; f < n; f++) if (c->slots[slot0 + f].fb.imeta) anyInter = 1;
   int useTeam = (anyInter ? (P.wpp ? n <= 96 : n <= 1024) : parallel <= 512) && wsCount >= HM_TEAM;
   { const char *ev = getenv("HM355_TEAM"); if (ev && ev[0] == '0') useTeam = 0; if (ev && ev[0] == '1' && wsCount >= HM_TEAM) useTeam = 1; }
+  // hm355_set_fast_decisions: the team protocol starts sub-CUs and partner candidates speculatively, which is not valid once candidates or
+  // sub-CUs may be cut short -- a P / B launch with any of the switches on is searched by one wavefront per CTU, whatever HM355_TEAM says
+  const int fast = P.esd | P.cfm << 1 | P.ecu << 2;
+  if (anyInter && fast) useTeam = 0;
   const size_t winSamples = (size_t)65 * P.stride[0] + (size_t)33 * (P.stride[1] + P.stride[2]);
   int teams = 0;
   int waves = anyInter ? HM_TEAM : HM_TEAM_I;   // P / B slices: every chain of candidates on two or three wavefronts (hm355_team.h)
@@ -524,12 +528,12 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     }
     teams = (int)(want < L.teamCap ? want : L.teamCap);
   }
-  if (fewWaves != L.fewWaves) {
+  if (fewWaves != L.fewWaves || fast != L.fast) {
     Params lp = c->hp; lp.ws = L.dWs; lp.fewWaves = fewWaves; lp.teamWin = L.dTeamWin; lp.teamWinStride = winSamples;
     if (l == 0) { c->hp.fewWaves = fewWaves; c->hp.teamWin = L.dTeamWin; c->hp.teamWinStride = winSamples; }
     HM_CHECK(c, hipMemcpyAsync(L.dP, &lp, sizeof(Params), hipMemcpyHostToDevice, L.stream));
     HM_CHECK(c, hipStreamSynchronize(L.stream));      // lp is a local
-    L.fewWaves = fewWaves;
+    L.fewWaves = fewWaves; L.fast = fast;
   }
   next_epoch(c);
   HM_CHECK(c, hipMemsetAsync(L.dSched, 0, 32, L.stream));       // ticket = 0, abort = 0, published CTUs = 0 (+ the counters of diagnostic builds)
@@ -647,6 +651,16 @@ extern "C" int hm355_set_lane_share(hm355_ctx *c, int launches_in_flight)
 {
   if (!c || launches_in_flight < 1 || launches_in_flight > HM_MAX_LANES) return HM355_ERR_ARG;
   c->laneShare = launches_in_flight;
+  return HM355_OK;
+}
+// Sticky state of the context (declared in include/hm355.h): it travels to the device in Params with the next launch of each lane
+extern "C" int hm355_set_fast_decisions(hm355_ctx *c, int esd, int cfm, int ecu)
+{
+  if (!c) return HM355_ERR_ARG;
+  if ((esd | cfm | ecu) & ~1) return fail(c, HM355_ERR_ARG, "hm355_set_fast_decisions: every switch is 0 or 1");
+  for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_fast_decisions: a slice is open (hm355_slice_end first)");
+  for (int l = 0; l < HM_MAX_LANES; l++) if (c->lane[l].busy) return fail(c, HM355_ERR_ARG, "hm355_set_fast_decisions: a launch is in flight (hm355_run_wait first)");
+  c->hp.esd = esd; c->hp.cfm = cfm; c->hp.ecu = ecu;
   return HM355_OK;
 }
 extern "C" int hm355_run_wait(hm355_ctx *c, int lane, double *kernel_ms)

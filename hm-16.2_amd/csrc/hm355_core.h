@@ -2654,7 +2654,10 @@ HM_DEV HM_NOINLINE void compress_ctu(Shared *e)
         f->bestBits += num_bits(&e->cur);
         f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
       }
-      if (cuDepth == 3) { restore_best(e, cuZ, cuDepth); retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue; }
+      // Params::ecu (early CU, TEncCu.cpp:867-874, :980): a CU inside the picture whose best mode is a skip has no split candidate and returns as
+      // the smallest CU size does, with the go-on coder as the split flag above left it
+      const int noSplit = cuDepth == 3 || (e->im && !f->boundary && HM_UNI(e->P->ecu) && HM_UNI(e->ws->best[cuDepth].im.skip[cuZ]));
+      if (noSplit) { restore_best(e, cuZ, cuDepth); retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue; }
       init_est_data(e, cuZ, cuDepth);
       f->splitBits = 0; f->splitDist = 0; f->sub = 0; f->phase = 1;
     }
@@ -2836,6 +2839,7 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
 #if !defined(HM355_HOSTSIM)
   // (a team hands the 64x64 candidate to a helper while it goes on: with m_bEncodeDQP set the later candidates would need to know whether that
   // one consumed it, so such a CTU -- rare -- is searched by the main wavefront alone)
+  // (hm355_set_fast_decisions: the host never launches a P / B slice with teams while a switch is on, hm355.hip's run_begin)
   if (team && e->im && !e->fb.dqp) compress_ctu_team_inter(e);
   else if (team && !e->im && !(e->fb.dqp && HM_UNI(e->ws->dq.flag))) compress_ctu_team(e); else
 #endif

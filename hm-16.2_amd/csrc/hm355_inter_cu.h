@@ -10,7 +10,8 @@ HM_DEV inline void check_best_mode(Shared *e, CuFrame *f, int cuZ, int cuDepth)
     cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]);
   }
 }
-HM_DEV HM_NOINLINE void check_rd_cost_merge_2Nx2N(Shared *e, int cuZ, int cuDepth, int sp)
+// returns earlyDetectionSkipMode (TEncCu.cpp:1497-1525; always 0 without ESD)
+HM_DEV HM_NOINLINE int check_rd_cost_merge_2Nx2N(Shared *e, int cuZ, int cuDepth, int sp)
 {
   HM_ENTRY(e); cuZ = HM_UNI(cuZ); cuDepth = HM_UNI(cuDepth); sp = HM_UNI(sp);
   CuFrame *f = &e->cuf[sp];
@@ -23,7 +24,7 @@ HM_DEV HM_NOINLINE void check_rd_cost_merge_2Nx2N(Shared *e, int cuZ, int cuDept
   for (int i = 0; i < 5; i++) { ml.dir[i] = e->ml.dir[i]; for (int l = 0; l < 2; l++) { ml.mv[i][l] = e->ml.f[i][l].mv; ml.ref[i][l] = e->ml.f[i][l].ref; } }
   ml.num = e->ml.num;
   int mergeCandBuffer[5] = {0, 0, 0, 0, 0};
-  int bestIsSkip = 0;
+  int bestIsSkip = 0, earlySkip = 0;
   MvD zero; zero.x = zero.y = 0;
   for (int noResidual = 0; noResidual < 2; noResidual++) {
     for (int cand = 0; cand < ml.num; cand++) {
@@ -41,7 +42,16 @@ HM_DEV HM_NOINLINE void check_rd_cost_merge_2Nx2N(Shared *e, int cuZ, int cuDept
       init_est_data(e, cuZ, cuDepth);
       if (!bestIsSkip) bestIsSkip = f->bestCost < HM_MAX_DOUBLE && !qt_root_cbf(&e->ws->best[cuDepth].m, cuZ);   // FDM
     }
+    if (noResidual == 0 && HM_UNI(e->P->esd)) { // the running best (the 2Nx2N search included) has no residual and is a merge or has a zero MVD
+      const Best *b = &e->ws->best[cuDepth];
+      if (!qt_root_cbf(&b->m, cuZ)) {
+        int absMvd = 0;
+        for (int l = 0; l < 2; l++) if (e->fb.ip->numRefIdx[l] > 0) { const MvD d = b->im.mvd[l][cuZ]; absMvd += (d.x < 0 ? -d.x : d.x) + (d.y < 0 ? -d.y : d.y); }
+        earlySkip = HM_UNI(b->im.mrg[cuZ] || absMvd == 0);
+      }
+    }
   }
+  return earlySkip;
 }
 HM_DEV HM_NOINLINE void check_rd_cost_inter(Shared *e, int cuZ, int cuDepth, int partSize, int useMRG, int sp)
 {
@@ -74,16 +84,28 @@ HM_DEV HM_NOINLINE void me_token_prepass(Shared *e, int cuZ, int cuDepth)
       motion_estimation(e, cuZ, cuDepth, SIZE_2Nx2N, 0, mvPred.x, mvPred.y, (list << 4) | ri, 0, 0, 0, 0, 1);
     }
 }
-// the mode tests of one CU in a P / B slice (TEncCu::xCompressCU :600-857 with ESD/CFM/ECU off)
+// the mode tests of one CU in a P / B slice (TEncCu::xCompressCU :600-857).  Params::esd: the 2Nx2N search runs before the merge check, and a
+// running best without residual that is a merge or has a zero MVD ends the CU's candidates, intra included (:630-643, :657).  Params::cfm: once
+// the running best has no residual (looked at after 2Nx2N, and after every later shape that became the best) no further inter shape is tested
+// (doNotBlockPu, :644-647 .. :798); intra is not gated.  Both 0: the order and the candidates of the default configuration.
 HM_DEV HM_NOINLINE void compress_cu_inter_modes(Shared *e, int cuZ, int cuDepth, int sp)
 {
   HM_ENTRY(e); cuZ = HM_UNI(cuZ); cuDepth = HM_UNI(cuDepth); sp = HM_UNI(sp);
   CuFrame *f = &e->cuf[sp];
+  int go = 1;                                                  // doNotBlockPu
   f->ampSens = 0;
-  { HM_PROF_BEGIN(e, PR_MRG2N); check_rd_cost_merge_2Nx2N(e, cuZ, cuDepth, sp); HM_PROF_END(e, PR_MRG2N); }
-  check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2Nx2N, 0, sp);
-  check_rd_cost_inter(e, cuZ, cuDepth, SIZE_Nx2N, 0, sp);
-  check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2NxN, 0, sp);
+  // (the switches are read where they are used and the running best is addressed anew each time: nothing more stays live across the candidates)
+#define HM_BEST_HAS_RESIDUAL() HM_UNI(qt_root_cbf(&e->ws->best[cuDepth].m, cuZ) != 0)
+  if (HM_UNI(e->P->esd)) check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2Nx2N, 0, sp);
+  int earlySkip;
+  { HM_PROF_BEGIN(e, PR_MRG2N); earlySkip = check_rd_cost_merge_2Nx2N(e, cuZ, cuDepth, sp); HM_PROF_END(e, PR_MRG2N); }
+  if (earlySkip) return;                                       // (ESD only: the 2Nx2N search ran in front)
+  if (!HM_UNI(e->P->esd)) { check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2Nx2N, 0, sp); if (HM_UNI(e->P->cfm)) go = HM_BEST_HAS_RESIDUAL(); }
+  // one later inter shape: tested unless blocked; under CFM the gate is updated when the shape is the running best (never after nRx2N, :776-778)
+#define HM_FAST_SHAPE(shape, mrg, last) do { if (go) { check_rd_cost_inter(e, cuZ, cuDepth, shape, mrg, sp); \
+    if (!(last) && HM_UNI(e->P->cfm) && e->ws->best[cuDepth].m.part[cuZ] == (shape)) go = HM_BEST_HAS_RESIDUAL(); } } while (0)
+  HM_FAST_SHAPE(SIZE_Nx2N, 0, 0);
+  HM_FAST_SHAPE(SIZE_2NxN, 0, 0);
   if (cuDepth < 3) { // deriveTestModeAMP :386-447 on the best mode so far
     const Best *b = &e->ws->best[cuDepth];
     const int ps = b->m.part[cuZ], bmrg = b->im.mrg[cuZ], bskip = b->im.skip[cuZ], parent = f->parentPart;
@@ -96,11 +118,13 @@ HM_DEV HM_NOINLINE void compress_cu_inter_modes(Shared *e, int cuZ, int cuDepth,
     if (ps == SIZE_2Nx2N && !bskip) { mh = 1; mv = 1; }
     if ((64 >> cuDepth) == 64) { hor = 0; ver = 0; }
     f->ampSens = (int8_t)((!hor && !mh) || (!ver && !mv));    // a parent with an AMP part size would add merge-only AMP candidates here (team search, hm355_team.h)
-    if (hor) { check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2NxnU, 0, sp); check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2NxnD, 0, sp); }
-    else if (mh) { check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2NxnU, 1, sp); check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2NxnD, 1, sp); }
-    if (ver) { check_rd_cost_inter(e, cuZ, cuDepth, SIZE_nLx2N, 0, sp); check_rd_cost_inter(e, cuZ, cuDepth, SIZE_nRx2N, 0, sp); }
-    else if (mv) { check_rd_cost_inter(e, cuZ, cuDepth, SIZE_nLx2N, 1, sp); check_rd_cost_inter(e, cuZ, cuDepth, SIZE_nRx2N, 1, sp); }
+    if (hor) { HM_FAST_SHAPE(SIZE_2NxnU, 0, 0); HM_FAST_SHAPE(SIZE_2NxnD, 0, 0); }
+    else if (mh) { HM_FAST_SHAPE(SIZE_2NxnU, 1, 0); HM_FAST_SHAPE(SIZE_2NxnD, 1, 0); }
+    if (ver) { HM_FAST_SHAPE(SIZE_nLx2N, 0, 0); HM_FAST_SHAPE(SIZE_nRx2N, 0, 1); }
+    else if (mv) { HM_FAST_SHAPE(SIZE_nLx2N, 1, 0); HM_FAST_SHAPE(SIZE_nRx2N, 1, 1); }
   }
+#undef HM_FAST_SHAPE
+#undef HM_BEST_HAS_RESIDUAL
   { // intra only when the best inter mode left a residual ("avoid very complex intra if it is unlikely", :820)
     const Best *b = &e->ws->best[cuDepth];
     if (b->m.cbf[0][cuZ] != 0 || b->m.cbf[1][cuZ] != 0 || b->m.cbf[2][cuZ] != 0) {

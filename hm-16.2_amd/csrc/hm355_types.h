@@ -159,6 +159,7 @@ struct Params {
   int32_t fewWaves;                  // the launch cannot fill the device: prefer the shortest dependency chain over the fewest instructions
   Pel *teamWin;                      // team launches: the helpers' private reconstruction windows, HM_TEAM_HELPERS per team (hm355_team.h)
   uint64_t teamWinStride;            // samples per helper window
+  int32_t esd, cfm, ecu;             // hm355_set_fast_decisions: early skip detection, CBF fast mode, early CU of P / B slices (TEncCu.cpp:630-657, :644-798, :867)
 };
 
 struct WorkItem { int32_t frame, ctuX, ctuY, pad; };

@@ -113,7 +113,7 @@ EXPORTS = ["hm355_build_id", "hm355_picture_stats_run", "hm355_picture_stats", "
            "hm355_compress_slice_inter", "hm355_compress_slices_inter", "hm355_deblock", "hm355_deblock_run", "hm355_ref_from_slot", "hm355_ref_release", "hm355_ref_bytes", "hm355_ref_export", "hm355_ref_import", "hm355_sao_run",
            "hm355_num_substreams", "hm355_encode_slices_run", "hm355_encode_slice",
            "hm355_upload_file_frames", "hm355_download_file_frames", "hm355_download_org",
-           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_dist_batch",
+           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_dist_batch",
            "hm355_transform_batch"]
 
 
@@ -138,6 +138,7 @@ def load_library(path=LIB_PATH):
     lib.hm355_run_begin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(SliceDesc)]
     lib.hm355_run_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
     lib.hm355_set_lane_share.argtypes = [C.c_void_p, C.c_int]
+    lib.hm355_set_fast_decisions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.hm355_set_dqp.argtypes = [C.c_void_p, C.c_int, C.POINTER(DqpDesc)]
     lib.hm355_get_dqp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
     lib.hm355_preanalyze.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -411,6 +412,10 @@ class Encoder:
 
     def set_lane_share(self, launches_in_flight):
         self._check(self.lib.hm355_set_lane_share(self.h_, int(launches_in_flight)), "hm355_set_lane_share")
+
+    def set_fast_decisions(self, esd=0, cfm=0, ecu=0):
+        """the reference's --ESD / --CFM / --ECU (each 0 or 1) for every later P / B search of this encoder; sticky until set again"""
+        self._check(self.lib.hm355_set_fast_decisions(self.h_, int(esd), int(cfm), int(ecu)), "hm355_set_fast_decisions")
 
     def run_wait(self, lane):
         """wait for the launch of `lane`; returns its kernel time in ms (hm355_run_wait)"""

@@ -28,6 +28,12 @@ Void TEncTop::create()
     if (m_ctx) hm355_destroy(m_ctx);
     exit(EXIT_FAILURE);
   }
+  // sticky state of the context: every compressSlice of a P / B slice from here on (TEncCu reads the three switches per CU, TEncCu.cpp:630-980)
+  if (hm355_set_fast_decisions(m_ctx, getUseEarlySkipDetection(), getUseCbfFastMode(), getUseEarlyCU()) != HM355_OK) {
+    fprintf(stderr, "TEncTop::create: %s\n", hm355_last_error(m_ctx));
+    hm355_destroy(m_ctx);
+    exit(EXIT_FAILURE);
+  }
 }
 Void TEncTop::destroy() { for (auto p : m_cListPic) { if (p->getDeviceRef()) hm355_ref_release(m_ctx, p->getDeviceRef()); delete p; } m_cListPic.clear(); if (m_ctx) hm355_destroy(m_ctx); m_ctx = nullptr; }
 Void TEncTop::init() { m_cGOPEncoder.init(this); m_cSliceEncoder.init(this); m_cLoopFilter.init(this); m_cEncSAO.init(this); }

@@ -122,6 +122,10 @@ public:
   Void setLoopFilterDisable(Bool b) { m_bLoopFilterDisable = b; } Bool getLoopFilterDisable() const { return m_bLoopFilterDisable; }
   Void setUseSAO(Bool b) { m_bUseSAO = b; } Bool getUseSAO() const { return m_bUseSAO; }
   Void setDecodedPictureHashSEIEnabled(Int b) { m_decodedPictureHashSEIEnabled = b; } Int getDecodedPictureHashSEIEnabled() const { return m_decodedPictureHashSEIEnabled; }   // --SEIDecodedPictureHash: 0 off, 1 MD5, 2 CRC, 3 checksum
+  // --ESD, --CFM, --ECU (TAppEncCfg.cpp:873-876): the fast encoder decisions of P / B slices; TEncTop::create hands them to hm355_set_fast_decisions
+  Void setUseEarlySkipDetection(Bool b) { m_useEarlySkipDetection = b; } Bool getUseEarlySkipDetection() const { return m_useEarlySkipDetection; }
+  Void setUseCbfFastMode(Bool b) { m_bUseCbfFastMode = b; } Bool getUseCbfFastMode() const { return m_bUseCbfFastMode; }
+  Void setUseEarlyCU(Bool b) { m_bUseEarlyCU = b; } Bool getUseEarlyCU() const { return m_bUseEarlyCU; }
   Int getPad(Int i) const { return m_aiPad[i]; }     // TEncCfg::m_aiPad: the driver feeds pictures of the coded size, so both are 0
   Int getSourceWidth() const { return m_iSourceWidth; } Int getSourceHeight() const { return m_iSourceHeight; }
   Int getQP() const { return m_iQP; } Int getGOPSize() const { return m_iGOPSize; } Int getIntraPeriod() const { return m_uiIntraPeriod; }
@@ -131,6 +135,7 @@ protected:
   Bool m_bLoopFilterDisable = true, m_bUseSAO = false;      // the loop filters are opt-in here (the reference's cfg files switch both on)
   Bool m_bUseAdaptiveQP = false; Int m_iQPAdaptationRange = 6;
   Int m_decodedPictureHashSEIEnabled = 0, m_aiPad[2] = { 0, 0 };
+  Bool m_useEarlySkipDetection = false, m_bUseCbfFastMode = false, m_bUseEarlyCU = false;
   GOPEntry m_GOPList[16]; Bool m_bUseHADME = true; UInt m_maxNumMergeCand = 5; Int m_TMVPModeId = 1;
 };
 

@@ -8,6 +8,9 @@
 //   ... hash=N as the last argument (N = 1 MD5, 2 CRC, 3 checksum: --SEIDecodedPictureHash) writes <dump.bin>.picstat: per picture in coding order one line with the
 //   two pieces of the reference's log line that depend on the picture, " [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB]" and " [MD5:...]" / " [CRC:...]" /
 //   " [Checksum:...]" (TEncGOP.cpp:2350, :1789-1802); the dump and the .bits file are what they are without it.
+//   ... fast=<esd><cfm><ecu> as a trailing argument (three digits 0 / 1, in front of hash=N when both are given): --ESD / --CFM / --ECU, the fast encoder
+//   decisions of P / B slices (TEncCfg::setUseEarlySkipDetection, setUseCbfFastMode, setUseEarlyCU -> hm355_set_fast_decisions).  Without the argument the
+//   environment variable HM355_FAST=<esd><cfm><ecu> is read the same way (for callers that build the command line themselves, such as bench.py --workload c3).
 // The slice data of every picture (TEncSlice::encodeSlice) goes to <dump.bin>.bits: per picture u32 numSubstreams, then per substream u32 size + bytes.
 #include "TEncTop.h"
 #include <stdio.h>
@@ -51,6 +54,13 @@ int main(int argc, char **argv)
   }
   const int hashMethod = argc > 9 && !strncmp(argv[argc - 1], "hash=", 5) ? atoi(argv[argc - 1] + 5) : 0;
   enc.setDecodedPictureHashSEIEnabled(hashMethod);
+  const char *fast = getenv("HM355_FAST");
+  if (fast) fprintf(stderr, "hm355_encmain: HM355_FAST=%s from the environment sets the fast decisions (a fast= argument overrides it)\n", fast);
+  for (int i = 9; i < argc; i++) if (!strncmp(argv[i], "fast=", 5)) fast = argv[i] + 5;
+  if (fast) {
+    if (strlen(fast) != 3 || strspn(fast, "01") != 3) { fprintf(stderr, "fast=<esd><cfm><ecu>: three digits 0 / 1\n"); return 2; }
+    enc.setUseEarlySkipDetection(fast[0] == '1'); enc.setUseCbfFastMode(fast[1] == '1'); enc.setUseEarlyCU(fast[2] == '1');
+  }
   enc.create(); enc.init();
   FILE *fs = hashMethod ? fopen((std::string(argv[8]) + ".picstat").c_str(), "w") : NULL;
   if (hashMethod && !fs) { perror("open"); return 1; }

@@ -296,6 +296,13 @@ int hm355_run_begin(hm355_ctx *ctx, int lane, int first_slot, int n, const hm355
  * run side by side instead of one after the other (a waiting persistent workgroup keeps its place on the CU) */
 int hm355_set_lane_share(hm355_ctx *ctx, int launches_in_flight);
 int hm355_run_wait(hm355_ctx *ctx, int lane, double *kernel_ms);
+/* The reference's fast encoder decisions for P / B slices, each 0 or 1 (default 0 / 0 / 0): --ESD early skip detection (TEncCu.cpp:630-643, :657,
+ * :1497-1525: the 2Nx2N search runs before the merge check; a best mode without residual that is a merge or has a zero MVD ends the CU's candidates),
+ * --CFM CBF fast mode (:644-647 .. :798: no further inter shape once the running best has no residual) and --ECU early CU (:867-874, :980: a CU
+ * whose best mode is a skip is not split).  The state is sticky and belongs to the context: it applies to every later search of a P / B slice
+ * (hm355_compress_slice(s)_inter, hm355_slice_begin_inter + hm355_run_ctus); I slices ignore it, whichever entry point searches them.  With any switch on, a P / B launch is searched by one wavefront per CTU (no wavefront teams, whatever HM355_TEAM says).
+ * HM355_ERR_ARG: a value other than 0 or 1; a slice open on any slot; a hm355_run_begin launch outstanding. */
+int hm355_set_fast_decisions(hm355_ctx *ctx, int esd, int cfm, int ecu);
 
 /* CTU-row bands (TEncSlice.cpp:740-755,855-858 are the WPP hand-off points a band boundary cuts through): a picture is
  * searched by several devices, each owning a band of whole CTU rows [first_row, last_row] of the pictures in slots
