@@ -26,6 +26,9 @@
 #include <math.h>
 #include <stdlib.h>
 #define HM_DEV static
+#define HM_FINL static inline
+#define HM_FINL_M inline
+#define HM_LAMBDA_INL
 #define HM_NOINLINE __attribute__((noinline))
 #define HM_CONST static const
 #define HM_ASSUME_LDS(p) ((void)0)
@@ -65,6 +68,9 @@ static inline int hm_wave_max_i(int v) { return v; }
 #define HM_ORDERED_CHAIN16(acc, a, b, pre) do { for (int k_ = 15; k_ >= 0; k_--) { pre[k_] = (acc); (acc) -= a[k_]; (acc) += b[k_]; } } while (0)
 #else
 #define HM_DEV __device__
+#define HM_FINL __device__ __forceinline__
+#define HM_FINL_M __device__ __forceinline__
+#define HM_LAMBDA_INL __attribute__((always_inline))
 #define HM_NOINLINE __attribute__((noinline))
 #define HM_CONST __device__ const
 /// address-space facts for pointers that arrive as generic function arguments / loaded values: lets the compiler
@@ -939,19 +945,18 @@ HM_DEV HM_NOINLINE void pred_intra(Shared *e, int comp, int mode, int n, int fil
   HM_SYNC();
 }
 
-// One predicted sample of `mode` at (x,y), straight from the reference lines in LDS: the same arithmetic as
-// pred_intra above, evaluated per sample so that a lane can own a whole (mode, 8x8 block) SATD task.
-HM_DEV inline int pred_sample(const Shared *e, int mode, int n, int l2, int x, int y, int dcVal, int bitDepth)
+// One predicted sample of `mode` at (x,y) of an n x n block, straight from the reference lines top / left: the arithmetic of
+// pred_intra above, evaluated per sample so that a lane can own a whole block.  edge: the DC / horizontal / vertical edge filters
+// (luma blocks up to 16x16).  The planar and DC constants fold where n is a compile-time argument.
+HM_FINL int intra_pred_sample(const Pel *top, const Pel *left, int n, int l2, int edge, int mode, int x, int y, int dcVal, int bitDepth)
 {
-  const int filt = use_filtered_refs(0, mode, n);
-  const Pel *top = e->u.ref.refTop[filt], *left = e->u.ref.refLeft[filt];
   if (mode == PLANAR_IDX) {
     const int hor = (left[y + 1] << l2) + n + (x + 1) * (top[n + 1] - left[y + 1]);
     const int ver = (top[x + 1] << l2) + (y + 1) * (left[n + 1] - top[x + 1]);
     return (hor + ver) >> (l2 + 1);
   }
   if (mode == DC_IDX) {
-    if (n <= 16) {
+    if (edge) {
       if (x == 0 && y == 0) return (top[1] + left[1] + 2 * dcVal + 2) >> 2;
       if (y == 0) return (top[x + 1] + 3 * dcVal + 2) >> 2;
       if (x == 0) return (left[y + 1] + 3 * dcVal + 2) >> 2;
@@ -966,7 +971,7 @@ HM_DEV inline int pred_sample(const Shared *e, int mode, int n, int l2, int x, i
   const int xx = isVer ? x : y, yy = isVer ? y : x;
   if (angle == 0) {
     int v = mainR[xx + 1];
-    if (n <= 16 && xx == 0) v = hm_clip3(0, (1 << bitDepth) - 1, v + ((sideR[yy + 1] - sideR[0]) >> 1));
+    if (edge && xx == 0) v = hm_clip3(0, (1 << bitDepth) - 1, v + ((sideR[yy + 1] - sideR[0]) >> 1));
     return v;
   }
   const int deltaPos = (yy + 1) * angle, di = deltaPos >> 5, df = deltaPos & 31;
@@ -977,6 +982,19 @@ HM_DEV inline int pred_sample(const Shared *e, int mode, int n, int l2, int x, i
   const int b = i1 >= 0 ? mainR[i1] : sideR[(128 - i1 * invAngle) >> 8];
   return ((32 - df) * a + df * b + 16) >> 5;
 }
+// a luma sample: the smoothed lines where the mode asks for them
+HM_DEV inline int pred_sample(const Shared *e, int mode, int n, int l2, int x, int y, int dcVal, int bitDepth)
+{
+  const int filt = use_filtered_refs(0, mode, n);
+  return intra_pred_sample(e->u.ref.refTop[filt], e->u.ref.refLeft[filt], n, l2, n <= 16, mode, x, y, dcVal, bitDepth);
+}
+// DC value of the reference lines in slot rs for an n x n block
+HM_FINL int ref_dc_val(const Shared *e, int rs, int n)
+{
+  int s = 0;
+  HM_PAR_FOR(i, n) s += e->u.ref.refTop[rs][i + 1] + e->u.ref.refLeft[rs][i + 1];
+  return (hm_wave_sum_i(s) + n) / (n + n);
+}
 
 // SATD of all 35 modes of an n x n luma PU (n <= 16): lanes own (mode, 8x8 block) tasks and predict their
 // samples on the fly, so the whole first-pass mode estimation of a small PU is one or a few wave passes.
@@ -984,9 +1002,7 @@ HM_DEV HM_NOINLINE void satd_all_modes_small(Shared *e, const Pel *org, int so, 
 {
   HM_ENTRY(e); so = HM_UNI(so); n = HM_UNI(n); org = hm_uni_ptr(org);
   const int l2 = hm_log2(n), bitDepth = e->bitDepth;
-  int s = 0;
-  HM_PAR_FOR(i, n) s += e->u.ref.refTop[0][i + 1] + e->u.ref.refLeft[0][i + 1];
-  const int dcVal = (hm_wave_sum_i(s) + n) / (n + n);
+  const int dcVal = ref_dc_val(e, 0, n);
   HM_PAR_FOR(i, 36) e->satd[i] = 0;
   HM_SYNC();
   if (n == 4) {
@@ -1046,15 +1062,19 @@ HM_DEV HM_NOINLINE void satd_all_modes_small(Shared *e, const Pel *org, int so, 
 // ------------------------------------------------------------------------------------------------
 // coefficient coding parameters
 // ------------------------------------------------------------------------------------------------
+HM_FINL int intra_scan_type(int mode)
+{ // the mode-dependent scan of a small intra block: within four of vertical -> horizontal scan, of horizontal -> vertical scan
+  if (hm_abs(mode - VER_IDX) <= 4) return SCAN_HOR;
+  if (hm_abs(mode - HOR_IDX) <= 4) return SCAN_VER;
+  return SCAN_DIAG;
+}
 HM_DEV inline int coef_scan_idx(const CtuMeta *m, int z, int n, int comp)
 {
   if (m->pred[z] != MODE_INTRA) return SCAN_DIAG; // TComDataCU::getCoefScanIdx, TComDataCU.cpp:3340-3380
   if (n > (comp ? 4 : 8)) return SCAN_DIAG;
   int dir = comp ? m->dirC[z] : m->dirL[z];
   if (dir == DM_CHROMA_IDX) dir = m->dirL[z & ~3];
-  if (hm_abs(dir - VER_IDX) <= 4) return SCAN_HOR;
-  if (hm_abs(dir - HOR_IDX) <= 4) return SCAN_VER;
-  return SCAN_DIAG;
+  return intra_scan_type(dir);
 }
 HM_DEV inline int first_sig_ctx(int n, int scanType, int chroma)
 { // getTUEntropyCodingParameters, TComChromaFormat.cpp:75-130
@@ -1119,21 +1139,49 @@ HM_DEV inline int hm_group_idx(int v)
 //   tOne  the 24 greater-than-1 contexts, then the 6 greater-than-2 contexts (lanes 48..59)
 //   tLast the 15 last-X contexts of the component, then its 15 last-Y contexts (lanes 30..59)
 //   tMisc the 4 coded-sub-block contexts, then the 10 cbf contexts (lanes 8..27)
-HM_DEV inline int ic_rate(HM_LVARG(int32_t, tOne), uint32_t absLevel, int ctxOne, int ctxAbs, int goRice, int c1Idx, int c2Idx)
-{ // xGetICRate, TComTrQuant.cpp:2725-2800
+struct LvPrices {                         // greater-than-1 / greater-than-2 prices in the lane variable tOne
+  HM_LVARG(int32_t, t);
+  HM_FINL_M int one(int i) const { return HM_LV_GET(t, i); }
+  HM_FINL_M int abs2(int i) const { return HM_LV_GET(t, 48 + i); }
+};
+// xWriteCoefRemainExGolomb, TEncSbac.cpp:337-375: length of the escape's exp-golomb suffix for symbol - (3 << rice); *symbol becomes the suffix
+HM_FINL uint32_t coef_remain_suffix(uint32_t *symbol, uint32_t goRice)
+{
+  uint32_t length = goRice;
+  while (*symbol >= (1u << length)) *symbol -= (1u << (length++));
+  return length;
+}
+HM_FINL uint32_t coef_remain_len(uint32_t symbol, uint32_t goRice)
+{ // bins of the whole code: unary prefix + rice suffix, or the escape (prefix of 4+ ones, exp-golomb suffix)
+  if (symbol < (3u << goRice)) return (symbol >> goRice) + 1 + goRice;
+  symbol -= (3u << goRice);
+  const uint32_t length = coef_remain_suffix(&symbol, goRice);
+  return 3 + length + 1 - goRice + length;
+}
+// The running state of the level chain inside a coefficient group (xRateDistOptQuant :2196-2225): greater-than-1 context, number of
+// levels coded so far with a greater-than-1 / greater-than-2 flag, Rice parameter.  A group starts from a fresh one.
+struct LevelChain {
+  int c1 = 1, c1Idx = 0, c2Idx = 0, goRice = 0;
+  HM_FINL_M void step(uint32_t level)
+  {
+    const uint32_t baseLevel = (c1Idx < 8) ? (2 + (c2Idx < 1)) : 1;
+    if (level >= baseLevel && level > (3u << goRice)) goRice = goRice + 1 < 4 ? goRice + 1 : 4;
+    if (level >= 1) c1Idx++;
+    if (level > 1) { c1 = 0; c2Idx++; }
+    else if (c1 < 3 && c1 > 0 && level) c1++;
+  }
+};
+// xGetICRate, TComTrQuant.cpp:2725-2800, at the chain's state; prices.one(i) / prices.abs2(i): bit cost of bin (i & 1) of greater-than-1 /
+// greater-than-2 context i >> 1
+template <class P> HM_FINL int ic_rate(const P &prices, uint32_t absLevel, int ctxOne, int ctxAbs, const LevelChain &ch)
+{
   int rate = 32768;
-  const uint32_t baseLevel = (c1Idx < 8) ? (2 + (c2Idx < 1)) : 1;
+  const uint32_t baseLevel = (ch.c1Idx < 8) ? (2 + (ch.c2Idx < 1)) : 1;
   if (absLevel >= baseLevel) {
-    uint32_t symbol = absLevel - baseLevel, length;
-    if (symbol < (3u << goRice)) { length = symbol >> goRice; rate += (int)((length + 1 + goRice) << 15); }
-    else {
-      length = (uint32_t)goRice; symbol -= (3u << goRice);
-      while (symbol >= (1u << length)) symbol -= (1u << (length++));
-      rate += (int)((3 + length + 1 - goRice + length) << 15);
-    }
-    if (c1Idx < 8) { rate += HM_LV_GET(tOne, ctxOne * 2 + 1); if (c2Idx < 1) rate += HM_LV_GET(tOne, 48 + ctxAbs * 2 + 1); }
-  } else if (absLevel == 1) rate += HM_LV_GET(tOne, ctxOne * 2);
-  else if (absLevel == 2) { rate += HM_LV_GET(tOne, ctxOne * 2 + 1); rate += HM_LV_GET(tOne, 48 + ctxAbs * 2); }
+    rate += (int)(coef_remain_len(absLevel - baseLevel, (uint32_t)ch.goRice) << 15);
+    if (ch.c1Idx < 8) { rate += prices.one(ctxOne * 2 + 1); if (ch.c2Idx < 1) rate += prices.abs2(ctxAbs * 2 + 1); }
+  } else if (absLevel == 1) rate += prices.one(ctxOne * 2);
+  else if (absLevel == 2) { rate += prices.one(ctxOne * 2 + 1); rate += prices.abs2(ctxAbs * 2); }
   else rate = 0;
   return rate;
 }
@@ -1264,7 +1312,8 @@ HM_DEV HM_NOINLINE int rdoq(Shared *e, TCoeff *dst, int n, int comp, int scanTyp
   double baseCost = blockUncodedCost;
   uint64_t cgMask = 0;                    // significant-coefficient-group flags, bit = raster position of the group
   const int cgLastScanPos = lastScanPos >> 4;
-  int ctxSet = ctx_set_index(chroma, lastScanPos >> 4, 0), c1 = 1, c2 = 0, c1Idx = 0, c2Idx = 0, goRice = 0;
+  int ctxSet = ctx_set_index(chroma, lastScanPos >> 4, 0);
+  LevelChain ch; const LvPrices prices = { tOne };
   for (int cgScanPos = cgLastScanPos; cgScanPos >= 0; cgScanPos--) {
     const int cgBlkPos = scanCG[cgScanPos], cgy = cgBlkPos >> (log2n - 2), cgx = cgBlkPos & (wg - 1);
     const uint64_t cgBit = 1ull << cgBlkPos;
@@ -1302,7 +1351,7 @@ HM_DEV HM_NOINLINE int rdoq(Shared *e, TCoeff *dst, int n, int comp, int scanTyp
       {
         const uint32_t maxAbsLevel = (uint32_t)HM_LV_GET(vMx, posInCG);
         const int32_t levelDouble = HM_LV_GET(vLvl, posInCG);
-        const int ctxOne = 4 * ctxSet + c1, ctxAbs = ctxSet;
+        const int ctxOne = 4 * ctxSet + ch.c1, ctxAbs = ctxSet;
         const int isLast = (scanPos == lastScanPos);
         int sigBits = 0, sigCode = 0;
         { // xGetCodedLevel, TComTrQuant.cpp:2660-2715
@@ -1315,7 +1364,7 @@ HM_DEV HM_NOINLINE int rdoq(Shared *e, TCoeff *dst, int n, int comp, int scanTyp
           for (int al = (int)maxAbsLevel; al >= (int)minAbs; al--) {
             const double de = (double)(levelDouble - (int32_t)((uint32_t)al << qBits));
             const double dist = de * de * errScale;
-            const double rc = lambda * (double)ic_rate(tOne, (uint32_t)al, ctxOne, ctxAbs, goRice, c1Idx, c2Idx);
+            const double rc = lambda * (double)ic_rate(prices, (uint32_t)al, ctxOne, ctxAbs, ch);
             double cc = dist + rc;
             cc += currCostSig;
             if (cc < cCoeff) { level = (uint32_t)al; cCoeff = cc; sigBits = currSigBits; sigCode = isLast ? 0 : 2; }
@@ -1324,11 +1373,7 @@ HM_DEV HM_NOINLINE int rdoq(Shared *e, TCoeff *dst, int n, int comp, int scanTyp
         cSig = lambda * (double)sigBits;
         HM_LV_SET(vCode, posInCG, sigCode); HM_LV_SET(vDec, posInCG, (int32_t)level);
         HM_LV_SETD(vCoef0, posInCG, cCoeff); HM_LV_SETD(vS0, posInCG, cSig);
-        const uint32_t baseLevel = (c1Idx < 8) ? (2 + (c2Idx < 1)) : 1;
-        if (level >= baseLevel && level > (3u << goRice)) goRice = goRice + 1 < 4 ? goRice + 1 : 4;
-        if (level >= 1) c1Idx++;
-        if (level > 1) { c1 = 0; c2 += (c2 < 2); c2Idx++; }
-        else if (c1 < 3 && c1 > 0 && level) c1++;
+        ch.step(level);
       }
       if (level) {
         HM_LV_SETD(vCC, posInCG, cCoeff);
@@ -1339,8 +1384,8 @@ HM_DEV HM_NOINLINE int rdoq(Shared *e, TCoeff *dst, int n, int comp, int scanTyp
       }
     }
     if (cgScanPos > 0) {                   // the next group starts a fresh context set
-      ctxSet = ctx_set_index(chroma, (cgScanPos * 16 - 1) >> 4, c1 == 0);
-      c1 = 1; c2 = 0; c1Idx = 0; c2Idx = 0; goRice = 0;
+      ctxSet = ctx_set_index(chroma, (cgScanPos * 16 - 1) >> 4, ch.c1 == 0);
+      ch = LevelChain();
     }
     // the three running sums of the reference, position by position from 15 down to 0
     HM_ORDERED_ADD16(baseCost, vCoef0);
@@ -1471,27 +1516,21 @@ HM_DEV HM_NOINLINE int rdoq(Shared *e, TCoeff *dst, int n, int comp, int scanTyp
           const int64_t I64MAX = 0x7fffffffffffffffLL;
           int64_t minCostInc = I64MAX, curCost = I64MAX; int minK = -1, finalChange = 0, curChange = 0;
           // re-walk the group's decision-time state (contexts, Rice parameter, flag counters)
-          int wC1 = 1, wC1Idx = 0, wC2Idx = 0, wGoR = 0; const int wSet = cgCtxSet[subSet];
+          LevelChain walk; const int wSet = cgCtxSet[subSet];
           const int kStart = (lastCG == 1 ? lastNZ : 15);
           for (int k = top; k >= 0; --k) {
             const uint32_t dec = (uint32_t)HM_LV_GET(sDec, k);
-            const int ctxOne = 4 * wSet + wC1, ctxSetD = wSet, goR = wGoR, c1I = wC1Idx, c2I = wC2Idx;
-            { // advance the walk past this position (same updates as the decision chain)
-              const uint32_t baseLevel = (wC1Idx < 8) ? (2 + (wC2Idx < 1)) : 1;
-              if (dec >= baseLevel && dec > (3u << wGoR)) wGoR = wGoR + 1 < 4 ? wGoR + 1 : 4;
-              if (dec >= 1) wC1Idx++;
-              if (dec > 1) { wC1 = 0; wC2Idx++; }
-              else if (wC1 < 3 && wC1 > 0 && dec) wC1++;
-            }
+            const int ctxOne = 4 * wSet + walk.c1, ctxSetD = wSet; const LevelChain at = walk;
+            walk.step(dec);                  // advance the walk past this position (same updates as the decision chain)
             if (k > kStart) continue;
             const int32_t lvlD = HM_LV_GET(sLvl, k);
             const int32_t deltaU = (int32_t)((lvlD - (int32_t)(dec << qBits)) >> (qBits - 8));
             const int sigRateDelta = HM_LV_GET(sDelta, k);
             int rateIncUp, rateIncDown = 0;
             if (dec > 0) {
-              const int rateNow = ic_rate(tOne, dec, ctxOne, ctxSetD, goR, c1I, c2I);
-              rateIncUp = ic_rate(tOne, dec + 1, ctxOne, ctxSetD, goR, c1I, c2I) - rateNow;
-              rateIncDown = ic_rate(tOne, dec - 1, ctxOne, ctxSetD, goR, c1I, c2I) - rateNow;
+              const int rateNow = ic_rate(prices, dec, ctxOne, ctxSetD, at);
+              rateIncUp = ic_rate(prices, dec + 1, ctxOne, ctxSetD, at) - rateNow;
+              rateIncDown = ic_rate(prices, dec - 1, ctxOne, ctxSetD, at) - rateNow;
             } else rateIncUp = HM_LV_GET(tOne, ctxOne * 2);
             const int dv = HM_LV_GET(sCur, k);
             if (dv != 0) {
@@ -1691,7 +1730,7 @@ template <class C> HM_DEV HM_NOINLINE void code_coeff_nxn(Shared *e, C *c, const
             uint32_t sym = (uint32_t)(a - baseLevel);
             // xWriteCoefRemainExGolomb :337: unary prefix + rice suffix, or the escape (prefix of 4+ ones, exp-golomb suffix)
             if (sym < (3u << goRice)) { const uint32_t len = sym >> goRice; enc_epv(&r, (((1u << (len + 1)) - 2) << goRice) | (sym & ((1u << goRice) - 1)), (int)(len + 1 + goRice)); }
-            else { uint32_t len = goRice; sym -= (3u << goRice); while (sym >= (1u << len)) sym -= (1u << (len++));
+            else { sym -= (3u << goRice); const uint32_t len = coef_remain_suffix(&sym, goRice);
                    if (real) { enc_epv(&r, (1u << (3 + len + 1 - goRice)) - 2, (int)(3 + len + 1 - goRice)); enc_epv(&r, sym, (int)len); }
                    else enc_epv(&r, 0, (int)(3 + len + 1 - goRice + len)); }
             if ((uint32_t)a > (3u << goRice)) goRice = goRice + 1 < 4 ? goRice + 1 : 4;
@@ -1900,7 +1939,7 @@ HM_DEV HM_NOINLINE uint32_t intra_coding_tu_block(Shared *e, TU tv, int comp, in
     const int y = i >> l2, x = i & (n - 1);
     const int r = org[y * ps + x] - pred[y * st + x];
     resi[y * st + x] = (Pel)r;
-    e->bufA[y * HM_TSTRIDE + x] = tskip ? (r << tshift) : r;         // xTransformSkip, TComTrQuant.cpp:1874
+    e->bufA[y * HM_TSTRIDE + x] = tskip ? r * (1 << tshift) : r;          // xTransformSkip, TComTrQuant.cpp:1874
   }
   HM_SYNC();
   { HM_PROF_BEGIN(e, PR_FWD); if (!tskip) fwd_transform(e, n, comp == 0 && n == 4, bitDepth); HM_PROF_END(e, PR_FWD); }      // TComTrQuant::xT, :1805
@@ -2130,6 +2169,7 @@ HM_DEV inline void set_intra_result_qt(Shared *e, const TU *root)
   }
 }
 
+#include "hm355_simt.h"
 #include "hm355_simt4.h"
 #include "hm355_simt8.h"
 
@@ -2396,8 +2436,8 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_chroma_qt(Shared *e, int cuZ, int cuD
     }
   }
   int bestMode = 0; uint32_t bestDist = 0; double bestCost = HM_MAX_DOUBLE;
-  int modeList[5] = {PLANAR_IDX, VER_IDX, HOR_IDX, DC_IDX, DM_CHROMA_IDX};       // getAllowedChromaDir, TComDataCU.cpp:1486
-  for (int i = 0; i < 4; i++) if (m->dirL[cuZ] == modeList[i]) { modeList[i] = 34; break; }
+  int modeList[5];
+  allowed_chroma_dirs(m->dirL[cuZ], modeList);
   for (int mi = 0; mi < 5; mi++) {
     cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
     par_set8(m->dirC + cuZ, modeList[mi], cuParts);
