@@ -2657,14 +2657,23 @@ HM_DEV HM_NOINLINE void check_rd_cost_intra(Shared *e, int cuZ, int cuDepth, int
 
 #include "hm355_inter_cu.h"
 
-// TEncCu::compressCtu -> xCompressCU recursion as a 4-level state machine
-HM_DEV HM_NOINLINE void compress_ctu(Shared *e)
+// TEncCu::compressCtu -> xCompressCU recursion as a 4-level state machine, written once for the three ways a CTU is searched.  The mode M
+// (WalkSolo below; WalkTeamI and WalkTeamPB in hm355_team.h) supplies what differs between them -- where the unsplit candidate of a CU is
+// evaluated and where its result is taken from -- and nothing else:
+//   kSplitPaysDqp                 the split candidate of the CTU prices its delta QP (TEncCu.cpp:1052-1085)
+//   unsplit(e, f, cuZ, d)         phase 0: evaluate or post the unsplit candidate; returns 1 when the CU has no split candidate (then the CU is in place)
+//   parent_part(e, f, cuZ, d)     the part size handed to a sub-CU for deriveTestModeAMP (TEncCu.cpp:1026)
+//   collect(e, f, cuZ, d)         before the split decision: the unsplit result is in f->best*; returns 1 to search the four sub-CUs again
+//   take_unsplit(e, cuZ, d)       the unsplit candidate is the CU (TComDataCU::copyToPic + xCopyYuv2Pic of the winner, TEncCu.cpp:1087-1110)
+//   may_stop_early(e, f, d)       after a sub-CU: the unsplit result is in f->best* and the exact early stop below is allowed
+// The order of reset_bits / enc_bin / num_bits / cabac_copy is part of the result (TEncBinCABACCounter::resetBits keeps the fractional bits).
+template <class M> HM_FINL void cu_walk(Shared *e)
 {
-  HM_ENTRY(e);
   CtuMeta *m = (&e->meta);
   CuFrame *fr = e->cuf; int sp = 0;
   fr[0].cuZ = 0; fr[0].phase = 0; fr[0].parentPart = SIZE_NONE;
   double retCost = 0; uint32_t retBits = 0, retDist = 0;
+  M mode;
   while (sp >= 0) {
     CuFrame *f = &fr[sp]; const int cuDepth = sp, cuZ = f->cuZ;
     const int size = 64 >> cuDepth, parts = 256 >> (2 * cuDepth), q = parts >> 2;
@@ -2673,31 +2682,7 @@ HM_DEV HM_NOINLINE void compress_ctu(Shared *e)
       const int lx = e->ctuX * 64 + (r & 15) * 4, ty = e->ctuY * 64 + (r >> 4) * 4;
       f->boundary = !((lx + size - 1 < e->width) && (ty + size - 1 < e->height));
       f->bestCost = HM_MAX_DOUBLE; f->bestBits = 0; f->bestDist = 0;
-      if (!f->boundary && e->im) { // P / B slice: TEncCu.cpp:628-836
-        { HM_PROF_BEGIN(e, PR_INTERCU); compress_cu_inter_modes(e, cuZ, cuDepth, sp); HM_PROF_END(e, PR_INTERCU); }
-        reset_bits(&e->cur);
-        if (cuDepth != 3) enc_bin(e, &e->cur, C_SPLIT + ctx_split_flag(e, cuZ, cuDepth), 0);
-        f->bestBits += num_bits(&e->cur);
-        f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
-      } else if (!f->boundary) {
-        check_rd_cost_intra(e, cuZ, cuDepth, SIZE_2Nx2N);
-        double c = e->outCost; uint32_t b = e->outBits, d = e->outDist;
-        if (c < f->bestCost) { f->bestCost = c; f->bestBits = b; f->bestDist = d; save_best(e, cuZ, cuDepth); cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]); }
-        if (cuDepth == 3) {
-          check_rd_cost_intra(e, cuZ, cuDepth, SIZE_NxN);
-          c = e->outCost; b = e->outBits; d = e->outDist;
-          if (c < f->bestCost) { f->bestCost = c; f->bestBits = b; f->bestDist = d; save_best(e, cuZ, cuDepth); cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]); }
-        }
-        // split flag of the unsplit candidate, TEncCu.cpp:859-863 (coded on the go-on coder as it stands)
-        reset_bits(&e->cur);
-        if (cuDepth != 3) enc_bin(e, &e->cur, C_SPLIT + ctx_split_flag(e, cuZ, cuDepth), 0);
-        f->bestBits += num_bits(&e->cur);
-        f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
-      }
-      // Params::ecu (early CU, TEncCu.cpp:867-874, :980): a CU inside the picture whose best mode is a skip has no split candidate and returns as
-      // the smallest CU size does, with the go-on coder as the split flag above left it
-      const int noSplit = cuDepth == 3 || (e->im && !f->boundary && HM_UNI(e->P->ecu) && HM_UNI(e->ws->best[cuDepth].im.skip[cuZ]));
-      if (noSplit) { restore_best(e, cuZ, cuDepth); retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue; }
+      if (mode.unsplit(e, f, cuZ, cuDepth)) { retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue; }
       init_est_data(e, cuZ, cuDepth);
       f->splitBits = 0; f->splitDist = 0; f->sub = 0; f->phase = 1;
     }
@@ -2713,19 +2698,19 @@ HM_DEV HM_NOINLINE void compress_ctu(Shared *e)
           if (s == 0) cabac_copy(&e->ws->slot[HM_SLOT(cuDepth + 1, CI_CURR_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
           else cabac_copy(&e->ws->slot[HM_SLOT(cuDepth + 1, CI_CURR_BEST)], &e->ws->slot[HM_SLOT(cuDepth + 1, CI_NEXT_BEST)]);
           fr[sp + 1].cuZ = (int16_t)subZ; fr[sp + 1].phase = 0;
-          // AMP speed-up: the part size of this depth's best mode when it is inter (rpcBestCU->isInter(0), TEncCu.cpp:1026)
-          fr[sp + 1].parentPart = (int8_t)((e->im && !f->boundary && e->ws->best[cuDepth].m.pred[cuZ] == MODE_INTER) ? e->ws->best[cuDepth].m.part[cuZ] : SIZE_NONE);
+          fr[sp + 1].parentPart = (int8_t)mode.parent_part(e, f, cuZ, cuDepth);
           f->phase = 2; sp++; continue;
         }
         continue;
       }
+      if (mode.collect(e, f, cuZ, cuDepth)) { init_est_data(e, cuZ, cuDepth); f->splitBits = 0; f->splitDist = 0; f->sub = 0; continue; }
       if (!f->boundary) {
         reset_bits(&e->cur);
         enc_bin(e, &e->cur, C_SPLIT + ctx_split_flag(e, cuZ, cuDepth), m->depth[cuZ] > cuDepth);
         f->splitBits += num_bits(&e->cur);
       }
       f->splitCost = calc_rd_cost(e, f->splitBits, f->splitDist);
-      if (e->fb.dqp && cuDepth == 0 && first_coded_cu(e) < 256) {   // the split candidate of quantisation-group size pays for its delta QP, TEncCu.cpp:1052-1085
+      if (M::kSplitPaysDqp && e->fb.dqp && cuDepth == 0 && first_coded_cu(e) < 256) {   // the split candidate of quantisation-group size pays for its delta QP
         reset_bits(&e->cur);
         code_delta_qp(e, &e->cur, HM_UNI(e->ws->dq.ctuQp) - HM_UNI(e->ws->dq.refQp));
         f->splitBits += num_bits(&e->cur);
@@ -2735,7 +2720,7 @@ HM_DEV HM_NOINLINE void compress_ctu(Shared *e)
       if (f->splitCost < f->bestCost) {
         f->bestCost = f->splitCost; f->bestBits = f->splitBits; f->bestDist = f->splitDist;
         cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]);
-      } else restore_best(e, cuZ, cuDepth);
+      } else mode.take_unsplit(e, cuZ, cuDepth);
       retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue;
     }
     if (f->phase == 2) { // a sub-CU returned
@@ -2747,23 +2732,63 @@ HM_DEV HM_NOINLINE void compress_ctu(Shared *e)
       // the estimator from its slot) follows it, or at the CTU root.
       // I slices only: in P / B slices the integer vector of the last 2Nx2N motion search seeds the next CU's search whatever CU that was
       // (m_integerMv2Nx2N, TEncSearch.cpp:3880-3888), so a skipped sub-CU would change its successors.
-      bool laterSibling = sp == 0;
-      if (sp > 0) {
-        const int pq = parts, pz = fr[sp - 1].cuZ;
-        for (int s2 = fr[sp - 1].sub; s2 < 4; s2++) {
-          const int r2 = hm_z2r(pz + s2 * pq);
-          laterSibling |= (e->ctuX * 64 + (r2 & 15) * 4 < e->width) && (e->ctuY * 64 + (r2 >> 4) * 4 < e->height);
+      if (f->sub < 4 && !f->boundary && mode.may_stop_early(e, f, cuDepth)) {
+        bool laterSibling = sp == 0;
+        if (sp > 0) {
+          const int pq = parts, pz = fr[sp - 1].cuZ;
+          for (int s2 = fr[sp - 1].sub; s2 < 4; s2++) {
+            const int r2 = hm_z2r(pz + s2 * pq);
+            laterSibling |= (e->ctuX * 64 + (r2 & 15) * 4 < e->width) && (e->ctuY * 64 + (r2 >> 4) * 4 < e->height);
+          }
         }
-      }
-      if (f->sub < 4 && !e->im && laterSibling && !f->boundary && !(calc_rd_cost(e, f->splitBits, f->splitDist) < f->bestCost)) {
-        restore_best(e, cuZ, cuDepth);
-        retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--;
+        if (laterSibling && !(calc_rd_cost(e, f->splitBits, f->splitDist) < f->bestCost)) {
+          mode.take_unsplit(e, cuZ, cuDepth);
+          retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--;
+        }
       }
       continue;
     }
   }
   e->outCost = retCost; e->outBits = retBits; e->outDist = retDist;
 }
+
+// one wavefront searches the CTU: every candidate in place, in the reference's order
+struct WalkSolo {
+  static constexpr bool kSplitPaysDqp = true;
+  HM_FINL_M int unsplit(Shared *e, CuFrame *f, int cuZ, int cuDepth)
+  {
+    if (!f->boundary) {
+      if (e->im) { HM_PROF_BEGIN(e, PR_INTERCU); compress_cu_inter_modes(e, cuZ, cuDepth, cuDepth); HM_PROF_END(e, PR_INTERCU); }   // P / B slice: TEncCu.cpp:628-836
+      else {
+        check_rd_cost_intra(e, cuZ, cuDepth, SIZE_2Nx2N);
+        double c = e->outCost; uint32_t b = e->outBits, d = e->outDist;
+        if (c < f->bestCost) { f->bestCost = c; f->bestBits = b; f->bestDist = d; save_best(e, cuZ, cuDepth); cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]); }
+        if (cuDepth == 3) {
+          check_rd_cost_intra(e, cuZ, cuDepth, SIZE_NxN);
+          c = e->outCost; b = e->outBits; d = e->outDist;
+          if (c < f->bestCost) { f->bestCost = c; f->bestBits = b; f->bestDist = d; save_best(e, cuZ, cuDepth); cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]); }
+        }
+      }
+      // split flag of the unsplit candidate, TEncCu.cpp:859-863 (coded on the go-on coder as it stands)
+      reset_bits(&e->cur);
+      if (cuDepth != 3) enc_bin(e, &e->cur, C_SPLIT + ctx_split_flag(e, cuZ, cuDepth), 0);
+      f->bestBits += num_bits(&e->cur);
+      f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
+    }
+    // Params::ecu (early CU, TEncCu.cpp:867-874, :980): a CU inside the picture whose best mode is a skip has no split candidate and returns as
+    // the smallest CU size does, with the go-on coder as the split flag above left it
+    const int noSplit = cuDepth == 3 || (e->im && !f->boundary && HM_UNI(e->P->ecu) && HM_UNI(e->ws->best[cuDepth].im.skip[cuZ]));
+    if (noSplit) restore_best(e, cuZ, cuDepth);
+    return noSplit;
+  }
+  // the part size of this depth's best mode when it is inter (rpcBestCU->isInter(0), TEncCu.cpp:1026)
+  HM_FINL_M int parent_part(Shared *e, const CuFrame *f, int cuZ, int cuDepth)
+  { return (e->im && !f->boundary && e->ws->best[cuDepth].m.pred[cuZ] == MODE_INTER) ? e->ws->best[cuDepth].m.part[cuZ] : SIZE_NONE; }
+  HM_FINL_M int collect(Shared *, CuFrame *, int, int) { return 0; }                                             // the unsplit result is in the frame since phase 0
+  HM_FINL_M void take_unsplit(Shared *e, int cuZ, int cuDepth) { restore_best(e, cuZ, cuDepth); }                      // from this wavefront's own best buffers
+  HM_FINL_M int may_stop_early(Shared *e, CuFrame *, int) { return !e->im; }                                           // I slices only, see cu_walk
+};
+HM_DEV HM_NOINLINE void compress_ctu(Shared *e) { HM_ENTRY(e); cu_walk<WalkSolo>(e); }
 
 // TEncCu::xEncodeCU, TEncCu.cpp:1185-1295: re-encode the decided CTU to advance the contexts
 template <class C> HM_DEV HM_NOINLINE void encode_ctu(Shared *e, C *c, int lastCtuOfSlice)

@@ -84,6 +84,23 @@ HM_DEV HM_NOINLINE void me_token_prepass(Shared *e, int cuZ, int cuDepth)
       motion_estimation(e, cuZ, cuDepth, SIZE_2Nx2N, 0, mvPred.x, mvPred.y, (list << 4) | ri, 0, 0, 0, 0, 1);
     }
 }
+// deriveTestModeAMP (TEncCu.cpp:386-447) on the best mode so far (part size ps, merge and skip flags) and the part size of the parent's best mode:
+// hor / ver: the full horizontal / vertical AMP pair is tested; mh / mv: else the merge-only pair.  ampSens: a parent with an AMP part size would
+// add merge-only AMP candidates here -- what the team search (hm355_team.h) needs to know of a CU searched before its parent's answer.
+struct AmpPlan { int hor, ver, mh, mv, ampSens; };
+HM_DEV inline AmpPlan derive_test_mode_amp(int ps, int bmrg, int bskip, int parent, int cuSize)
+{
+  AmpPlan a; a.hor = a.ver = a.mh = a.mv = 0;
+  if (ps == SIZE_2NxN) a.hor = 1;
+  else if (ps == SIZE_Nx2N) a.ver = 1;
+  else if (ps == SIZE_2Nx2N && !bmrg && !bskip) { a.hor = 1; a.ver = 1; }
+  if (parent >= SIZE_2NxnU && parent <= SIZE_nRx2N) { a.mh = 1; a.mv = 1; }
+  if (parent == SIZE_NONE) { if (ps == SIZE_2NxN) a.mh = 1; else if (ps == SIZE_Nx2N) a.mv = 1; }
+  if (ps == SIZE_2Nx2N && !bskip) { a.mh = 1; a.mv = 1; }
+  if (cuSize == 64) { a.hor = 0; a.ver = 0; }
+  a.ampSens = (!a.hor && !a.mh) || (!a.ver && !a.mv);
+  return a;
+}
 // the mode tests of one CU in a P / B slice (TEncCu::xCompressCU :600-857).  Params::esd: the 2Nx2N search runs before the merge check, and a
 // running best without residual that is a merge or has a zero MVD ends the CU's candidates, intra included (:630-643, :657).  Params::cfm: once
 // the running best has no residual (looked at after 2Nx2N, and after every later shape that became the best) no further inter shape is tested
@@ -106,18 +123,11 @@ HM_DEV HM_NOINLINE void compress_cu_inter_modes(Shared *e, int cuZ, int cuDepth,
     if (!(last) && HM_UNI(e->P->cfm) && e->ws->best[cuDepth].m.part[cuZ] == (shape)) go = HM_BEST_HAS_RESIDUAL(); } } while (0)
   HM_FAST_SHAPE(SIZE_Nx2N, 0, 0);
   HM_FAST_SHAPE(SIZE_2NxN, 0, 0);
-  if (cuDepth < 3) { // deriveTestModeAMP :386-447 on the best mode so far
+  if (cuDepth < 3) {
     const Best *b = &e->ws->best[cuDepth];
-    const int ps = b->m.part[cuZ], bmrg = b->im.mrg[cuZ], bskip = b->im.skip[cuZ], parent = f->parentPart;
-    int hor = 0, ver = 0, mh = 0, mv = 0;
-    if (ps == SIZE_2NxN) hor = 1;
-    else if (ps == SIZE_Nx2N) ver = 1;
-    else if (ps == SIZE_2Nx2N && !bmrg && !bskip) { hor = 1; ver = 1; }
-    if (parent >= SIZE_2NxnU && parent <= SIZE_nRx2N) { mh = 1; mv = 1; }
-    if (parent == SIZE_NONE) { if (ps == SIZE_2NxN) mh = 1; else if (ps == SIZE_Nx2N) mv = 1; }
-    if (ps == SIZE_2Nx2N && !bskip) { mh = 1; mv = 1; }
-    if ((64 >> cuDepth) == 64) { hor = 0; ver = 0; }
-    f->ampSens = (int8_t)((!hor && !mh) || (!ver && !mv));    // a parent with an AMP part size would add merge-only AMP candidates here (team search, hm355_team.h)
+    const AmpPlan a = derive_test_mode_amp(b->m.part[cuZ], b->im.mrg[cuZ], b->im.skip[cuZ], f->parentPart, 64 >> cuDepth);
+    const int hor = a.hor, ver = a.ver, mh = a.mh, mv = a.mv;
+    f->ampSens = (int8_t)a.ampSens;
     if (hor) { HM_FAST_SHAPE(SIZE_2NxnU, 0, 0); HM_FAST_SHAPE(SIZE_2NxnD, 0, 0); }
     else if (mh) { HM_FAST_SHAPE(SIZE_2NxnU, 1, 0); HM_FAST_SHAPE(SIZE_2NxnD, 1, 0); }
     if (ver) { HM_FAST_SHAPE(SIZE_nLx2N, 0, 0); HM_FAST_SHAPE(SIZE_nRx2N, 0, 1); }

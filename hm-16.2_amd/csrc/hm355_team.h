@@ -66,7 +66,7 @@ __device__ __forceinline__ void team_st(uint32_t *p, uint32_t v) { if (hm_lane()
 #define HM_TEAM_RELEASE() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
 #define HM_TEAM_ACQUIRE() do { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 
-#if defined(HM355_TEAMSTAT)            /* diagnostic build (tools/): where the main wavefront's time goes, summed over the CTUs of a launch into the scheduler words */
+#if defined(HM355_TEAMSTAT)            /* diagnostic build (-DHM355_TEAMSTAT, no tool drives it): where the main wavefront's time goes, summed over the CTUs of a launch into the scheduler words; hm355.hip's run_wait prints them */
 #define HM_TSTAT_ADD(k, v) do { if (hm_lane() == 0) atomicAdd((unsigned int *)HM_TEAM_PTR()->abortWord + 2 + (k), (unsigned int)(v)); } while (0)
 #define HM_TSTAT_T0(t) const unsigned long long t = wall_clock64()
 #define HM_TSTAT_T1(k, t) HM_TSTAT_ADD(k, (wall_clock64() - (t)) >> 7)
@@ -114,120 +114,68 @@ HM_DEV inline WorkSpace *team_wave_ws(int wave) { return HM_TEAM_PTR()->sh[0].ws
 // the workspace that holds the answer of helper h (box index): its own or its partner's
 HM_DEV inline WorkSpace *team_answer_ws(Shared *e, int h) { return team_wave_ws(HM_UNI(HM_TEAM_PTR()->box[h].owner)); }
 
-// what the reference's xCheckBestMode does when the unsplit candidate is the best mode: results of the helper become the CU's
-HM_DEV inline void team_take_unsplit(Shared *e, int h, int cuZ, int cuDepth)
+// the candidate a helper answered with (box index h) becomes the frame's best so far, as xCheckBestMode sees it
+HM_DEV inline void team_collect(CuFrame *f, int h)
 {
-  WorkSpace *hw = e->im ? team_answer_ws(e, h) : team_helper_ws(e, h);
-  restore_best_from(e, &hw->best[cuDepth], cuZ, cuDepth);
-  cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &hw->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)]);
+  const TeamBox *b = &HM_TEAM_PTR()->box[h];
+  f->bestCost = b->cost; f->bestBits = b->bits; f->bestDist = b->dist;
+}
+// TEncSearch::m_integerMv2Nx2N ([list][reference index]) from one workspace to another; the caller's HM_SYNC() ends the hand-over
+HM_DEV inline void intmv_copy(MvD (*dst)[16], const MvD (*src)[16]) { HM_PAR_FOR(i, 32) dst[i >> 4][i & 15] = src[i >> 4][i & 15]; }
+// what the reference's xCheckBestMode does when the unsplit candidate is the best mode: the results in workspace `owner` (a helper's) become the CU's
+HM_DEV inline void team_take_unsplit(Shared *e, const WorkSpace *owner, int cuZ, int cuDepth)
+{
+  restore_best_from(e, &owner->best[cuDepth], cuZ, cuDepth);
+  cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &owner->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)]);
 }
 
-// TEncCu::compressCtu -> xCompressCU for an I slice, the unsplit candidates evaluated by the helpers (see the head of this file)
-HM_DEV HM_NOINLINE void compress_ctu_team(Shared *e)
-{
-  HM_ENTRY(e);
-  CtuMeta *m = (&e->meta);
-  CuFrame *fr = e->cuf; int sp = 0;
-  fr[0].cuZ = 0; fr[0].phase = 0; fr[0].parentPart = SIZE_NONE;
-  double retCost = 0; uint32_t retBits = 0, retDist = 0;
-  int pending[4] = {0, 0, 0, 0};       // the unsplit candidate of this depth is with its helper
-  while (sp >= 0) {
-    CuFrame *f = &fr[sp]; const int cuDepth = sp, cuZ = f->cuZ;
-    const int size = 64 >> cuDepth, parts = 256 >> (2 * cuDepth), q = parts >> 2;
-    if (f->phase == 0) {
-      const int r = hm_z2r(cuZ);
-      const int lx = e->ctuX * 64 + (r & 15) * 4, ty = e->ctuY * 64 + (r >> 4) * 4;
-      f->boundary = !((lx + size - 1 < e->width) && (ty + size - 1 < e->height));
-      f->bestCost = HM_MAX_DOUBLE; f->bestBits = 0; f->bestDist = 0;
-      pending[cuDepth] = 0;
-      if (!f->boundary) {
-        team_post(e, cuDepth, cuZ, cuDepth, SIZE_2Nx2N);
-        pending[cuDepth] = 1;
-        if (cuDepth == 3) {
-          // the helper has the 2Nx2N candidate; the NxN one runs here.  xCheckBestMode sees 2Nx2N first, NxN has to be strictly cheaper.
-          check_rd_cost_intra(e, cuZ, cuDepth, SIZE_NxN);
-          const double cN = e->outCost; const uint32_t bN = e->outBits, dN = e->outDist;
-          team_wait(e, 3); pending[3] = 0;
-          const TeamBox *b = &HM_TEAM_PTR()->box[3];
-          f->bestCost = b->cost; f->bestBits = b->bits; f->bestDist = b->dist;
-          if (cN < f->bestCost) {
-            f->bestCost = cN; f->bestBits = bN; f->bestDist = dN;
-            save_best(e, cuZ, cuDepth);
-            cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]);
-            restore_best(e, cuZ, cuDepth);
-          } else team_take_unsplit(e, 3, cuZ, cuDepth);
-          reset_bits(&e->cur);           // TEncCu.cpp:859-863 at the smallest CU size: no split flag, the bit counter is reset all the same
-          f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
-          retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue;
-        }
-      }
-      init_est_data(e, cuZ, cuDepth);
-      f->splitBits = 0; f->splitDist = 0; f->sub = 0; f->phase = 1;
-    }
-    if (f->phase == 1) {
-      if (f->sub < 4) {
-        const int s = f->sub++;
-        const int subZ = cuZ + s * q, r = hm_z2r(subZ);
-        const int sx = e->ctuX * 64 + (r & 15) * 4, sy = e->ctuY * 64 + (r >> 4) * 4;
-        HM_PAR_FOR(i, q) { m->depth[subZ + i] = (uint8_t)(cuDepth + 1); m->part[subZ + i] = SIZE_NONE; m->pred[subZ + i] = MODE_NONE; }
-        HM_SYNC();
-        if (sx < e->width && sy < e->height) {
-          if (s == 0) cabac_copy(&e->ws->slot[HM_SLOT(cuDepth + 1, CI_CURR_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
-          else cabac_copy(&e->ws->slot[HM_SLOT(cuDepth + 1, CI_CURR_BEST)], &e->ws->slot[HM_SLOT(cuDepth + 1, CI_NEXT_BEST)]);
-          fr[sp + 1].cuZ = (int16_t)subZ; fr[sp + 1].phase = 0; fr[sp + 1].parentPart = SIZE_NONE;
-          f->phase = 2; sp++; continue;
-        }
-        continue;
-      }
-      if (!f->boundary) {
-        reset_bits(&e->cur);
-        enc_bin(e, &e->cur, C_SPLIT + ctx_split_flag(e, cuZ, cuDepth), m->depth[cuZ] > cuDepth);
-        f->splitBits += num_bits(&e->cur);
-      }
-      f->splitCost = calc_rd_cost(e, f->splitBits, f->splitDist);
-      if (e->fb.dqp && cuDepth == 0 && first_coded_cu(e) < 256) {   // the split candidate of quantisation-group size pays for its delta QP, TEncCu.cpp:1052-1085
-        reset_bits(&e->cur);
-        code_delta_qp(e, &e->cur, HM_UNI(e->ws->dq.ctuQp) - HM_UNI(e->ws->dq.refQp));
-        f->splitBits += num_bits(&e->cur);
-        f->splitCost = calc_rd_cost(e, f->splitBits, f->splitDist);
-      }
-      cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)], &e->ws->slot[HM_SLOT(cuDepth + 1, CI_NEXT_BEST)]);
-      if (pending[cuDepth]) {
-        team_wait(e, cuDepth); pending[cuDepth] = 0;
-        const TeamBox *b = &HM_TEAM_PTR()->box[cuDepth];
-        f->bestCost = b->cost; f->bestBits = b->bits; f->bestDist = b->dist;
-      }
-      if (f->splitCost < f->bestCost) {
-        f->bestCost = f->splitCost; f->bestBits = f->splitBits; f->bestDist = f->splitDist;
-        cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]);
-      } else team_take_unsplit(e, cuDepth, cuZ, cuDepth);
-      retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue;
-    }
-    if (f->phase == 2) { // a sub-CU returned
-      f->splitBits += retBits; f->splitDist += retDist; f->phase = 1;
-      // the exact early stop of compress_ctu (same conditions), applied when the unsplit result is already there
-      if (pending[cuDepth] && team_ready(e, cuDepth)) {
-        pending[cuDepth] = 0;
-        const TeamBox *b = &HM_TEAM_PTR()->box[cuDepth];
-        f->bestCost = b->cost; f->bestBits = b->bits; f->bestDist = b->dist;
-      }
-      bool laterSibling = sp == 0;
-      if (sp > 0) {
-        const int pq = parts, pz = fr[sp - 1].cuZ;
-        for (int s2 = fr[sp - 1].sub; s2 < 4; s2++) {
-          const int r2 = hm_z2r(pz + s2 * pq);
-          laterSibling |= (e->ctuX * 64 + (r2 & 15) * 4 < e->width) && (e->ctuY * 64 + (r2 >> 4) * 4 < e->height);
-        }
-      }
-      if (!pending[cuDepth] && f->sub < 4 && laterSibling && !f->boundary && !(calc_rd_cost(e, f->splitBits, f->splitDist) < f->bestCost)) {
-        team_take_unsplit(e, cuDepth, cuZ, cuDepth);
-        retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--;
-      }
-      continue;
-    }
+// one flag per CU depth, held in a register (an array indexed by the depth at run time would live in scratch memory)
+struct DepthFlags {
+  unsigned bits = 0;
+  HM_FINL_M int operator[](int d) const { return (int)((bits >> d) & 1u); }
+  HM_FINL_M void set(int d, int on) { bits = (bits & ~(1u << d)) | ((unsigned)(on != 0) << d); }
+};
+
+// cu_walk (hm355_core.h) for an I slice, the unsplit candidates evaluated by the helpers (see the head of this file)
+struct WalkTeamI {
+  static constexpr bool kSplitPaysDqp = true;   // as WalkSolo: a dqp picture comes here unless m_bEncodeDQP is set (process_ctu)
+  DepthFlags pending;                           // the unsplit candidate of this depth is with its helper
+  HM_FINL_M int unsplit(Shared *e, CuFrame *f, int cuZ, int cuDepth)
+  {
+    pending.set(cuDepth, 0);
+    if (f->boundary) return 0;
+    team_post(e, cuDepth, cuZ, cuDepth, SIZE_2Nx2N);
+    pending.set(cuDepth, 1);
+    if (cuDepth != 3) return 0;
+    // the helper has the 2Nx2N candidate; the NxN one runs here.  xCheckBestMode sees 2Nx2N first, NxN has to be strictly cheaper.
+    check_rd_cost_intra(e, cuZ, cuDepth, SIZE_NxN);
+    const double cN = e->outCost; const uint32_t bN = e->outBits, dN = e->outDist;
+    team_wait(e, 3); pending.set(3, 0);
+    team_collect(f, 3);
+    if (cN < f->bestCost) {
+      f->bestCost = cN; f->bestBits = bN; f->bestDist = dN;
+      save_best(e, cuZ, cuDepth);
+      cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]);
+      restore_best(e, cuZ, cuDepth);
+    } else take_unsplit(e, cuZ, cuDepth);
+    reset_bits(&e->cur);           // TEncCu.cpp:859-863 at the smallest CU size: no split flag, the bit counter is reset all the same
+    f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
+    return 1;
   }
-  e->outCost = retCost; e->outBits = retBits; e->outDist = retDist;
-}
+  HM_FINL_M int parent_part(Shared *, const CuFrame *, int, int) { return SIZE_NONE; }                                 // no inter candidates: deriveTestModeAMP never runs
+  HM_FINL_M int collect(Shared *e, CuFrame *f, int, int cuDepth)
+  { // xCheckBestMode :1702 compares against the helper's result: wait for it
+    if (pending[cuDepth]) { team_wait(e, cuDepth); pending.set(cuDepth, 0); team_collect(f, cuDepth); }
+    return 0;
+  }
+  HM_FINL_M void take_unsplit(Shared *e, int cuZ, int cuDepth) { team_take_unsplit(e, team_helper_ws(e, cuDepth), cuZ, cuDepth); }   // helper d holds the candidate of depth d
+  HM_FINL_M int may_stop_early(Shared *e, CuFrame *f, int cuDepth)
+  { // only when the helper has already answered: the stop never changes a result, so the answer's timing does not matter
+    if (pending[cuDepth] && team_ready(e, cuDepth)) { pending.set(cuDepth, 0); team_collect(f, cuDepth); }
+    return !pending[cuDepth];
+  }
+};
+HM_DEV HM_NOINLINE void compress_ctu_team(Shared *e) { HM_ENTRY(e); cu_walk<WalkTeamI>(e); }
 
 // The mode tests of one CU in a P / B slice (compress_cu_inter_modes, hm355_inter_cu.h) by two wavefronts: this one takes the merge and 2Nx2N
 // candidates, the horizontal AMP pair and the intra candidates, its partner (wave `mate`) Nx2N / 2NxN and the vertical AMP pair.  Every candidate
@@ -248,8 +196,8 @@ HM_DEV HM_NOINLINE int compress_cu_inter_modes_duo(Shared *e, int cuZ, int cuDep
     const int i = hm_lane() & 31;
     const MvD keep = e->ws->intMv[i >> 4][i & 15];
     me_token_prepass(e, cuZ, cuDepth);
-    HM_PAR_FOR(k, 32) mw->intMv[k >> 4][k & 15] = e->ws->intMv[k >> 4][k & 15];
-    if (mate2) { WorkSpace *mw2 = team_wave_ws(mate2); HM_PAR_FOR(k, 32) mw2->intMv[k >> 4][k & 15] = e->ws->intMv[k >> 4][k & 15]; }
+    intmv_copy(mw->intMv, e->ws->intMv);
+    if (mate2) intmv_copy(team_wave_ws(mate2)->intMv, e->ws->intMv);
     HM_SYNC();
     if (hm_lane() < 32) e->ws->intMv[i >> 4][i & 15] = keep;
     HM_SYNC();
@@ -259,28 +207,21 @@ HM_DEV HM_NOINLINE int compress_cu_inter_modes_duo(Shared *e, int cuZ, int cuDep
   check_rd_cost_merge_2Nx2N(e, cuZ, cuDepth, sp);
   check_rd_cost_inter(e, cuZ, cuDepth, SIZE_2Nx2N, 0, sp);
   team_wait(e, mate - 1);
-  if (HM_UNI(mb->improved) && mb->cost < f->bestCost) { f->bestCost = mb->cost; f->bestBits = mb->bits; f->bestDist = mb->dist; owner = mate; }
+  if (HM_UNI(mb->improved) && mb->cost < f->bestCost) { team_collect(f, mate - 1); owner = mate; }
   if (mate2) {                          // 2NxN follows Nx2N in the reference's order
     team_wait(e, mate2 - 1);
     mb = &HM_TEAM_PTR()->box[mate2 - 1];
-    if (HM_UNI(mb->improved) && mb->cost < f->bestCost) { f->bestCost = mb->cost; f->bestBits = mb->bits; f->bestDist = mb->dist; owner = mate2; }
+    if (HM_UNI(mb->improved) && mb->cost < f->bestCost) { team_collect(f, mate2 - 1); owner = mate2; }
   }
   // TEncBinCABACCounter::resetBits keeps the fractional bits (TEncBinCoderCABAC.cpp:161), so what follows the candidates on the go-on coder "as it
   // stands" (the split flags, TEncCu.cpp:859-863, :1042-1047) sees the remainder the LAST candidate in the reference's order left -- the partner's, here
   int mateLast = 1; uint32_t mateFrac = (uint32_t)HM_UNI(mb->sens);
   mb = &HM_TEAM_PTR()->box[mate - 1];
-  if (cuDepth < 3) { // deriveTestModeAMP :386-447 on the best mode so far
+  if (cuDepth < 3) {
     const Best *b = &team_wave_ws(owner)->best[cuDepth];
-    const int ps = HM_UNI(b->m.part[cuZ]), bmrg = HM_UNI(b->im.mrg[cuZ]), bskip = HM_UNI(b->im.skip[cuZ]), parent = f->parentPart;
-    int hor = 0, ver = 0, mh = 0, mv = 0;
-    if (ps == SIZE_2NxN) hor = 1;
-    else if (ps == SIZE_Nx2N) ver = 1;
-    else if (ps == SIZE_2Nx2N && !bmrg && !bskip) { hor = 1; ver = 1; }
-    if (parent >= SIZE_2NxnU && parent <= SIZE_nRx2N) { mh = 1; mv = 1; }
-    if (parent == SIZE_NONE) { if (ps == SIZE_2NxN) mh = 1; else if (ps == SIZE_Nx2N) mv = 1; }
-    if (ps == SIZE_2Nx2N && !bskip) { mh = 1; mv = 1; }
-    if ((64 >> cuDepth) == 64) { hor = 0; ver = 0; }
-    f->ampSens = (int8_t)((!hor && !mh) || (!ver && !mv));
+    const AmpPlan a = derive_test_mode_amp(HM_UNI(b->m.part[cuZ]), HM_UNI(b->im.mrg[cuZ]), HM_UNI(b->im.skip[cuZ]), f->parentPart, 64 >> cuDepth);
+    const int hor = a.hor, ver = a.ver, mh = a.mh, mv = a.mv;
+    f->ampSens = (int8_t)a.ampSens;
     const int mateBusy = ver || mv;
     if (mateBusy) team_post(e, mate - 1, cuZ, cuDepth, ver ? 1 : 2, TK_PAIR2, self, f->bestCost);
     const double before = f->bestCost;
@@ -290,7 +231,7 @@ HM_DEV HM_NOINLINE int compress_cu_inter_modes_duo(Shared *e, int cuZ, int cuDep
     if (hor || mh) mateLast = 0;
     if (mateBusy) {
       team_wait(e, mate - 1);
-      if (HM_UNI(mb->improved) && mb->cost < f->bestCost) { f->bestCost = mb->cost; f->bestBits = mb->bits; f->bestDist = mb->dist; owner = mate; }
+      if (HM_UNI(mb->improved) && mb->cost < f->bestCost) { team_collect(f, mate - 1); owner = mate; }
       mateLast = 1; mateFrac = (uint32_t)HM_UNI(mb->sens);
     }
   }
@@ -308,124 +249,84 @@ HM_DEV HM_NOINLINE int compress_cu_inter_modes_duo(Shared *e, int cuZ, int cuDep
   return owner;
 }
 
-// TEncCu::compressCtu -> xCompressCU for a P / B slice: the unsplit CUs of depth 0..2 with the helpers, the 8x8 CUs here (see the head of this file)
+// cu_walk (hm355_core.h) for a P / B slice: the unsplit CUs of depth 0..2 with the helpers, the 8x8 CUs here (see the head of this file)
+struct WalkTeamPB {
+  static constexpr bool kSplitPaysDqp = false;  // process_ctu never sends a dqp picture here
+  DepthFlags pending;                           // the unsplit CU of this depth is with its helper
+  DepthFlags guessed;                           // a sub-CU of this depth's CU started before the helper had answered: its parent part size was taken as "not AMP"
+  DepthFlags sensitive;                         // ... and its candidate list would have been another one under an AMP parent
+  HM_FINL_M int unsplit(Shared *e, CuFrame *f, int cuZ, int cuDepth)
+  {
+    if (cuDepth == 3) {               // TEncCu.cpp:628-863 at the smallest CU size, as WalkSolo does it (no split flag, the bit counter is reset all the same)
+      if (!f->boundary) {
+        HM_TSTAT_T0(t8);
+        const int owner = compress_cu_inter_modes_duo(e, cuZ, cuDepth, cuDepth, 0, 4, 8);
+        HM_TSTAT_T1(3, t8);
+        reset_bits(&e->cur);
+        f->bestBits += num_bits(&e->cur);
+        f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
+        if (owner != 0) team_take_unsplit(e, team_wave_ws(owner), cuZ, cuDepth);   // the partner's candidate won: its workspace holds the CU
+        else restore_best(e, cuZ, cuDepth);
+      } else restore_best(e, cuZ, cuDepth);
+      return 1;
+    }
+    pending.set(cuDepth, 0); guessed.set(cuDepth, 0); sensitive.set(cuDepth, 0);
+    if (!f->boundary) {
+      intmv_copy(team_helper_ws(e, cuDepth)->intMv, e->ws->intMv);                  // m_integerMv2Nx2N as the unsplit CU finds it
+      HM_SYNC();
+      team_post(e, cuDepth, cuZ, cuDepth, f->parentPart);
+      pending.set(cuDepth, 1);
+      me_token_prepass(e, cuZ, cuDepth);                                             // ... and as it leaves it
+      intmv_copy(e->ws->teamTok[cuDepth], e->ws->intMv);
+      HM_SYNC();
+    }
+    return 0;
+  }
+  // the part size of this depth's best mode when it is inter (TEncCu.cpp:1026) -- known once the helper has answered, else taken as "not AMP"
+  HM_FINL_M int parent_part(Shared *e, CuFrame *f, int cuZ, int cuDepth)
+  {
+    if (f->boundary) return SIZE_NONE;
+    if (pending[cuDepth] && team_ready(e, cuDepth)) { pending.set(cuDepth, 0); team_collect(f, cuDepth); }
+    if (pending[cuDepth]) { guessed.set(cuDepth, 1); return SIZE_NONE; }
+    return answered_part(e, cuZ, cuDepth);
+  }
+  HM_FINL_M int answered_part(Shared *e, int cuZ, int cuDepth)
+  {
+    const Best *hb = &team_answer_ws(e, cuDepth)->best[cuDepth];
+    return HM_UNI(hb->m.pred[cuZ]) == MODE_INTER ? HM_UNI(hb->m.part[cuZ]) : SIZE_NONE;
+  }
+  HM_FINL_M int collect(Shared *e, CuFrame *f, int cuZ, int cuDepth)
+  { // xCheckBestMode :1702 compares against the helper's result: wait for it
+    if (pending[cuDepth]) {
+      HM_TSTAT_T0(tw);
+      team_wait(e, cuDepth); pending.set(cuDepth, 0);
+      HM_TSTAT_T1(2, tw);
+      team_collect(f, cuDepth);
+    }
+    if (!f->boundary && guessed[cuDepth] && sensitive[cuDepth]) {
+      const int pp = answered_part(e, cuZ, cuDepth);
+      if (pp >= SIZE_2NxnU && pp <= SIZE_nRx2N) {
+        // the guess was wrong where it mattered: the sub-CUs again, from the state the unsplit CU's 2Nx2N search left (nothing outside this CU has read them)
+        intmv_copy(e->ws->intMv, e->ws->teamTok[cuDepth]);
+        HM_SYNC();
+        guessed.set(cuDepth, 0); sensitive.set(cuDepth, 0);
+        HM_TSTAT_ADD(4, 1);
+        return 1;
+      }
+    }
+    // a CU searched before its parent's answer: would an AMP parent have changed the candidate list of its unsplit CU (CuFrame::ampSens)?
+    if (cuDepth > 0 && !f->boundary && HM_UNI(HM_TEAM_PTR()->box[cuDepth].sens)) sensitive.set(cuDepth - 1, 1);
+    return 0;
+  }
+  HM_FINL_M void take_unsplit(Shared *e, int cuZ, int cuDepth) { team_take_unsplit(e, team_answer_ws(e, cuDepth), cuZ, cuDepth); }   // helper d or its partner holds the best mode of depth d
+  HM_FINL_M int may_stop_early(Shared *, CuFrame *, int) { return 0; }                                                  // never: a skipped sub-CU would change m_integerMv2Nx2N for its successors
+};
 HM_DEV HM_NOINLINE void compress_ctu_team_inter(Shared *e)
 {
   HM_ENTRY(e);
   HM_TSTAT_T0(tAll);
-  CtuMeta *m = (&e->meta);
-  CuFrame *fr = e->cuf; int sp = 0;
-  fr[0].cuZ = 0; fr[0].phase = 0; fr[0].parentPart = SIZE_NONE;
-  double retCost = 0; uint32_t retBits = 0, retDist = 0;
-  int pending[3] = {0, 0, 0};          // the unsplit CU of this depth is with its helper
-  int guessed[3] = {0, 0, 0};          // a sub-CU of this depth's CU started before the helper had answered: its parent part size was taken as "not AMP"
-  int sensitive[3] = {0, 0, 0};        // ... and its candidate list would have been another one under an AMP parent
-  while (sp >= 0) {
-    CuFrame *f = &fr[sp]; const int cuDepth = sp, cuZ = f->cuZ;
-    const int size = 64 >> cuDepth, parts = 256 >> (2 * cuDepth), q = parts >> 2;
-    if (f->phase == 0) {
-      const int r = hm_z2r(cuZ);
-      const int lx = e->ctuX * 64 + (r & 15) * 4, ty = e->ctuY * 64 + (r >> 4) * 4;
-      f->boundary = !((lx + size - 1 < e->width) && (ty + size - 1 < e->height));
-      f->bestCost = HM_MAX_DOUBLE; f->bestBits = 0; f->bestDist = 0;
-      if (cuDepth == 3) {               // TEncCu.cpp:628-863 at the smallest CU size, as compress_ctu does it
-        if (!f->boundary) {
-          HM_TSTAT_T0(t8);
-          const int owner = compress_cu_inter_modes_duo(e, cuZ, cuDepth, sp, 0, 4, 8);
-          HM_TSTAT_T1(3, t8);
-          reset_bits(&e->cur);
-          f->bestBits += num_bits(&e->cur);
-          f->bestCost = calc_rd_cost(e, f->bestBits, f->bestDist);
-          if (owner != 0) {              // the partner's candidate won: its workspace holds the CU (as team_take_unsplit)
-            WorkSpace *ow = team_wave_ws(owner);
-            restore_best_from(e, &ow->best[cuDepth], cuZ, cuDepth);
-            cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &ow->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)]);
-          } else restore_best(e, cuZ, cuDepth);
-        } else restore_best(e, cuZ, cuDepth);
-        retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue;
-      }
-      pending[cuDepth] = 0; guessed[cuDepth] = 0; sensitive[cuDepth] = 0;
-      if (!f->boundary) {
-        WorkSpace *hw = team_helper_ws(e, cuDepth);
-        HM_PAR_FOR(i, 32) hw->intMv[i >> 4][i & 15] = e->ws->intMv[i >> 4][i & 15];   // m_integerMv2Nx2N as the unsplit CU finds it
-        HM_SYNC();
-        team_post(e, cuDepth, cuZ, cuDepth, f->parentPart);
-        pending[cuDepth] = 1;
-        me_token_prepass(e, cuZ, cuDepth);                                             // ... and as it leaves it
-        HM_PAR_FOR(i, 32) e->ws->teamTok[cuDepth][i >> 4][i & 15] = e->ws->intMv[i >> 4][i & 15];
-        HM_SYNC();
-      }
-      init_est_data(e, cuZ, cuDepth);
-      f->splitBits = 0; f->splitDist = 0; f->sub = 0; f->phase = 1;
-    }
-    if (f->phase == 1) {
-      if (f->sub < 4) {
-        const int s = f->sub++;
-        const int subZ = cuZ + s * q, r = hm_z2r(subZ);
-        const int sx = e->ctuX * 64 + (r & 15) * 4, sy = e->ctuY * 64 + (r >> 4) * 4;
-        HM_PAR_FOR(i, q) { m->depth[subZ + i] = (uint8_t)(cuDepth + 1); m->part[subZ + i] = SIZE_NONE; m->pred[subZ + i] = MODE_NONE; }
-        HM_SYNC();
-        if (sx < e->width && sy < e->height) {
-          if (s == 0) cabac_copy(&e->ws->slot[HM_SLOT(cuDepth + 1, CI_CURR_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
-          else cabac_copy(&e->ws->slot[HM_SLOT(cuDepth + 1, CI_CURR_BEST)], &e->ws->slot[HM_SLOT(cuDepth + 1, CI_NEXT_BEST)]);
-          fr[sp + 1].cuZ = (int16_t)subZ; fr[sp + 1].phase = 0;
-          // AMP speed-up: the part size of this depth's best mode when it is inter (TEncCu.cpp:1026) -- known once the helper has answered
-          int parentPart = SIZE_NONE;
-          if (!f->boundary) {
-            if (pending[cuDepth] && team_ready(e, cuDepth)) {
-              pending[cuDepth] = 0;
-              const TeamBox *b = &HM_TEAM_PTR()->box[cuDepth];
-              f->bestCost = b->cost; f->bestBits = b->bits; f->bestDist = b->dist;
-            }
-            if (!pending[cuDepth]) {
-              const Best *hb = &team_answer_ws(e, cuDepth)->best[cuDepth];
-              if (HM_UNI(hb->m.pred[cuZ]) == MODE_INTER) parentPart = HM_UNI(hb->m.part[cuZ]);
-            } else guessed[cuDepth] = 1;
-          }
-          fr[sp + 1].parentPart = (int8_t)parentPart;
-          f->phase = 2; sp++; continue;
-        }
-        continue;
-      }
-      if (pending[cuDepth]) {
-        HM_TSTAT_T0(tw);
-        team_wait(e, cuDepth); pending[cuDepth] = 0;
-        HM_TSTAT_T1(2, tw);
-        const TeamBox *b = &HM_TEAM_PTR()->box[cuDepth];
-        f->bestCost = b->cost; f->bestBits = b->bits; f->bestDist = b->dist;
-      }
-      if (!f->boundary && guessed[cuDepth] && sensitive[cuDepth]) {
-        const Best *hb = &team_answer_ws(e, cuDepth)->best[cuDepth];
-        const int pp = HM_UNI(hb->m.pred[cuZ]) == MODE_INTER ? HM_UNI(hb->m.part[cuZ]) : SIZE_NONE;
-        if (pp >= SIZE_2NxnU && pp <= SIZE_nRx2N) {
-          // the guess was wrong where it mattered: the sub-CUs again, from the state the unsplit CU's 2Nx2N search left (nothing outside this CU has read them)
-          HM_PAR_FOR(i, 32) e->ws->intMv[i >> 4][i & 15] = e->ws->teamTok[cuDepth][i >> 4][i & 15];
-          HM_SYNC();
-          guessed[cuDepth] = 0; sensitive[cuDepth] = 0;
-          HM_TSTAT_ADD(4, 1);
-          init_est_data(e, cuZ, cuDepth);
-          f->splitBits = 0; f->splitDist = 0; f->sub = 0;
-          continue;
-        }
-      }
-      if (!f->boundary) {
-        reset_bits(&e->cur);
-        enc_bin(e, &e->cur, C_SPLIT + ctx_split_flag(e, cuZ, cuDepth), m->depth[cuZ] > cuDepth);
-        f->splitBits += num_bits(&e->cur);
-      }
-      f->splitCost = calc_rd_cost(e, f->splitBits, f->splitDist);
-      cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)], &e->ws->slot[HM_SLOT(cuDepth + 1, CI_NEXT_BEST)]);
-      if (f->splitCost < f->bestCost) {
-        f->bestCost = f->splitCost; f->bestBits = f->splitBits; f->bestDist = f->splitDist;
-        cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]);
-      } else team_take_unsplit(e, cuDepth, cuZ, cuDepth);
-      if (sp > 0 && !f->boundary) sensitive[sp - 1] |= HM_UNI(HM_TEAM_PTR()->box[cuDepth].sens);
-      retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue;
-    }
-    if (f->phase == 2) { f->splitBits += retBits; f->splitDist += retDist; f->phase = 1; continue; }   // a sub-CU returned
-  }
+  cu_walk<WalkTeamPB>(e);
   HM_TSTAT_T1(1, tAll); HM_TSTAT_ADD(0, 1);
-  e->outCost = retCost; e->outBits = retBits; e->outDist = retDist;
 }
 
 // ---- helper wavefront `wave` (1 .. HM_TEAM - 1) ----

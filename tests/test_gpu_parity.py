@@ -49,13 +49,9 @@ def test_hip_matches_oracle_on_fresh_inputs(built, hm, w, h, bd, qp, wpp, seed):
     enc.close()
 
 
-@pytest.mark.parametrize("team", ["0", "1"])
-@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES)
-def test_hip_p_and_b_slices_match_reference_fixture(hm, monkeypatch, name, team):
-    """low-delay P, random access and low-delay B clips: every P / B slice through hm355_compress_slice_inter with the reference
-    pictures and slice parameters the reference's compressSlice saw; decisions, motion, coefficients, costs, reconstruction bit-exact --
-    searched by one wavefront per CTU (team 0) and by a team of wavefronts per CTU (team 1, hm355_team.h: what a one-picture launch gets)."""
-    monkeypatch.setenv("HM355_TEAM", team)
+def _p_and_b_slices_match_reference_fixture(hm, name):
+    """every P / B slice of clip `name` through hm355_compress_slice_inter with the reference pictures and slice parameters the reference's
+    compressSlice saw; decisions, motion, coefficients, costs, reconstruction bit-exact"""
     cfg, slices, finals = common.load_ldp_case(name)
     enc = hm.Encoder(cfg["width"], cfg["height"], cfg["bit_depth"], cfg["wpp"], max_batch=1)
     n_p = 0
@@ -72,6 +68,24 @@ def test_hip_p_and_b_slices_match_reference_fixture(hm, monkeypatch, name, team)
         n_p += 1
     assert n_p >= 3
     enc.close()
+
+
+@pytest.mark.parametrize("team", ["0", "1"])
+@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES)
+def test_hip_p_and_b_slices_match_reference_fixture(hm, monkeypatch, name, team):
+    """low-delay P, random access and low-delay B clips against the reference fixture (see _p_and_b_slices_match_reference_fixture) --
+    searched by one wavefront per CTU (team 0) and by a team of wavefronts per CTU (team 1, hm355_team.h: what a one-picture launch gets)."""
+    monkeypatch.setenv("HM355_TEAM", team)
+    _p_and_b_slices_match_reference_fixture(hm, name)
+
+
+@pytest.mark.parametrize("name", ["ldp_200x136_8b_qp24", "ldb_200x136_8b_qp30"])
+def test_hip_p_and_b_slices_with_five_wavefront_teams_match_reference_fixture(hm, monkeypatch, name):
+    """a P / B launch searched by teams of five wavefronts (HM355_TEAM_WAVES=5: no partners, compress_cu_inter_modes_duo hands the whole candidate
+    chain of a CU to compress_cu_inter_modes on the wavefront that has it) on one P and one B clip with boundary CUs: the same fixture, bit-exact."""
+    monkeypatch.setenv("HM355_TEAM", "1")
+    monkeypatch.setenv("HM355_TEAM_WAVES", "5")
+    _p_and_b_slices_match_reference_fixture(hm, name)
 
 
 def test_hip_p_slice_batch_equals_single(hm):
