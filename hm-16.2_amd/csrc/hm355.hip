@@ -278,6 +278,7 @@ struct hm355_ctx {
   std::vector<Slot> slots;
   Lane lane[HM_MAX_LANES];   // lane 0 is built with the context and serves every blocking entry point; 1.. are built on first use
   double lastKernelMs = 0; int lastLaunches = 0, laneShare = 1;
+  hm355_launch_shape lastShape = {};   // hm355_last_launch_shape
   std::string err;
   int numCtus = 0;
   DevBuf<DbkParams> dDbk;      // [max_batch] deblocking parameters of the pictures in the slots
@@ -299,14 +300,6 @@ static void next_epoch(hm355_ctx *c) { c->epoch++; if (c->epoch == 0) c->epoch =
 extern "C" const char *hm355_build_id(void) { return HM355_BUILD_ID; }
 extern "C" const char *hm355_last_error(const hm355_ctx *ctx) { return ctx ? ctx->err.c_str() : "no context"; }
 
-static int maxItemsPerStep(int wCtu, int hCtu, int wpp, int frames)
-{
-  if (!wpp) return frames;
-  int best = 0;
-  for (int s = 0; s < wCtu + 2 * (hCtu - 1); s++) { int c = 0; for (int y = 0; y < hCtu; y++) { int x = s - 2 * y; if (x >= 0 && x < wCtu) c++; } if (c > best) best = c; }
-  return best * frames;
-}
-
 // Lane l of the context: its stream, events, scratch areas, scheduler words and parameter block.  hm355_create builds lane 0 (a blocking stream:
 // the entry points that are not searches run on it too; its dP is the context's Params, which every other kernel reads); further lanes are
 // built on first use with a non-blocking stream.  dWs is not initialised.
@@ -316,9 +309,8 @@ static int lane_init(hm355_ctx *c, int l)
   if (L.stream) return HM355_OK;
   HM_CHECK(c, l == 0 ? hipStreamCreate(&L.stream) : hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
   HM_CHECK(c, hipEventCreate(&L.ev0)); HM_CHECK(c, hipEventCreate(&L.ev1));
-  // one scratch area per resident workgroup of the persistent grid: 256 CUs x 8 single-wave workgroups, or fewer when the batch is small
-  size_t wsCount = (size_t)c->numCtus * (size_t)c->cfg.max_batch * HM_TEAM; if (wsCount > 3072) wsCount = 3072;   // 12 searches per CU x 256 CUs is the most that can be resident; a small batch runs as teams of HM_TEAM wavefronts per CTU
-  HM_CHECK(c, L.dWs.alloc(wsCount));
+  // one scratch area per search the persistent grid can hold, or fewer when the batch is small (hm355_ws_count, hm355_host_common.h)
+  HM_CHECK(c, L.dWs.alloc((size_t)hm355_ws_count(c->numCtus, c->cfg.max_batch)));
   HM_CHECK(c, L.dSched.ensure(16, true));         // 64 bytes, zeroed by a synchronous hipMemset
   HM_CHECK(c, L.dP.alloc(1));
   return HM355_OK;
@@ -493,41 +485,24 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     HM_CHECK(c, hipMemcpyAsync(L.dItems, L.items.data(), sizeof(WorkItem) * L.items.size(), hipMemcpyHostToDevice, L.stream));
     memcpy(L.key, key, sizeof(key)); L.keyValid = 1;
   }
-  // A WPP picture offers about 16 CTUs at a time (one when the CABAC state chains through all of them).  A launch that cannot keep ~5
-  // one-wavefront searches per CU busy prefers the shortest dependency chain over the fewest instructions (fewWaves); one that cannot
-  // even give every CU two searches runs as teams of HM_TEAM wavefronts per CTU (HM355_TEAM=0 / 1 overrides for A/B runs).
-  // P / B slices: a team (nine wavefronts, one team per CU) takes a one-stream picture through 3x faster than one wavefront per CTU, and 256 teams together do about half of
-  // what 2,816 one-wavefront searches do: measured on 1080p low-delay P streams with WaveFrontSynchro (CTU/s, one wavefront / teams): 32 streams
-  // 798 / 1,556, 64: 1,538 / 2,356, 128: 2,862 / 2,944 -- teams up to 96 streams (1,024 when every stream is one serial chain of CTUs).
-  const long long parallel = (long long)n * (P.wpp ? 16 : 1);
-  const int fewWaves = parallel < 1280 ? 1 : 0;
-  const size_t wsCount = L.dWs.n;
+  // the launch shape (hm355_plan_launch, hm355_host_common.h: which kernel, how many workgroups, Params::fewWaves)
   int anyInter = 0;
   for (int f = 0; f < n; f++) if (c->slots[slot0 + f].fb.imeta) anyInter = 1;
-  int useTeam = (anyInter ? (P.wpp ? n <= 96 : n <= 1024) : parallel <= 512) && wsCount >= HM_TEAM;
-  { const char *ev = getenv("HM355_TEAM"); if (ev && ev[0] == '0') useTeam = 0; if (ev && ev[0] == '1' && wsCount >= HM_TEAM) useTeam = 1; }
-  // hm355_set_fast_decisions: the team protocol starts sub-CUs and partner candidates speculatively, which is not valid once candidates or
-  // sub-CUs may be cut short -- a P / B launch with any of the switches on is searched by one wavefront per CTU, whatever HM355_TEAM says
   const int fast = P.esd | P.cfm << 1 | P.ecu << 2;
-  if (anyInter && fast) useTeam = 0;
+  int envTeam = -1, envTeamWaves = 0;
+  { const char *ev = getenv("HM355_TEAM"); if (ev && (ev[0] == '0' || ev[0] == '1')) envTeam = ev[0] - '0'; }
+  { const char *ev = getenv("HM355_TEAM_WAVES"); if (ev) envTeamWaves = atoi(ev); }
   const size_t winSamples = (size_t)65 * P.stride[0] + (size_t)33 * (P.stride[1] + P.stride[2]);
-  int teams = 0;
-  int waves = anyInter ? HM_TEAM : HM_TEAM_I;   // P / B slices: every chain of candidates on two or three wavefronts (hm355_team.h)
-  { const char *ev = getenv("HM355_TEAM_WAVES"); if (ev && atoi(ev) == HM_TEAM_I) waves = HM_TEAM_I; }   // A/B runs (five-wavefront teams on P streams: 1,021 / 1,529 / 1,871 CTU/s in the table above)
-  if (useTeam) {
-    const size_t total = L.items.size();
-    // as many teams as CTUs can ever be ready at once (the wavefront's widest step), a few more so that a finished team finds the next ticket taken
-    const int rows = ctu1 / P.wCtu - ctu0 / P.wCtu + 1;
-    size_t want = (size_t)maxItemsPerStep(P.wCtu, rows < P.hCtu ? rows : P.hCtu, P.wpp, n) + 2;
-    if (want > total) want = total; if (want > 512) want = 512; if (want > wsCount / waves) want = wsCount / waves;
-    if (want > L.teamCap) {   // the windows grow only after the lane's stream is idle; without them the launch runs without teams
-      HM_CHECK(c, hipStreamSynchronize(L.stream));
-      L.teamCap = 0; L.fewWaves = -1;
-      if (L.dTeamWin.alloc(want * HM_TEAM_HELPERS * winSamples) != hipSuccess) { (void)hipGetLastError(); useTeam = 0; }
-      else L.teamCap = want;
-    }
-    teams = (int)(want < L.teamCap ? want : L.teamCap);
+  hm355_launch_plan plan = hm355_plan_launch(P.wCtu, P.hCtu, P.wpp, c->cfg.max_batch, n, ctu0, ctu1, anyInter, fast, envTeam, envTeamWaves, c->laneShare, (long long)L.teamCap);
+  if ((size_t)plan.wsCount != L.dWs.n || (size_t)plan.total != L.items.size()) return fail(c, HM355_ERR_DEVICE, "hm355: the launch plan does not match the lane");
+  if (plan.teamWanted && (size_t)plan.want > L.teamCap) {   // the windows grow only after the lane's stream is idle; without them the launch runs without teams
+    HM_CHECK(c, hipStreamSynchronize(L.stream));
+    L.teamCap = 0; L.fewWaves = -1;
+    if (L.dTeamWin.alloc((size_t)plan.want * HM_TEAM_HELPERS * winSamples) != hipSuccess) (void)hipGetLastError();
+    else L.teamCap = (size_t)plan.want;
+    plan = hm355_plan_launch(P.wCtu, P.hCtu, P.wpp, c->cfg.max_batch, n, ctu0, ctu1, anyInter, fast, envTeam, envTeamWaves, c->laneShare, (long long)L.teamCap);
   }
+  const int fewWaves = plan.fewWaves, waves = plan.waves;
   if (fewWaves != L.fewWaves || fast != L.fast) {
     Params lp = c->hp; lp.ws = L.dWs; lp.fewWaves = fewWaves; lp.teamWin = L.dTeamWin; lp.teamWinStride = winSamples;
     if (l == 0) { c->hp.fewWaves = fewWaves; c->hp.teamWin = L.dTeamWin; c->hp.teamWinStride = winSamples; }
@@ -541,25 +516,21 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     for (int f = 0; f < n; f++) HM_CHECK(c, hipMemsetD32Async((hipDeviceptr_t)c->slots[slot0 + f].fb.done, (int)c->epoch, ctu0, L.stream));
   L.prepared = slices == NULL;
   HM_CHECK(c, hipEventRecord(L.ev0, L.stream));
-  const int total = (int)L.items.size();
-  if (useTeam && teams > 0) {
-    L.grid = teams;
+  const int total = plan.total;
+  L.grid = plan.grid;
+  if (plan.useTeam) {
     const size_t lds = HM_TEAM_LDS_BYTES(waves);
     if (!c->teamLdsSet) { HM_CHECK(c, hipFuncSetAttribute((const void *)hm355_ctu_team_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)HM_TEAM_LDS_BYTES(HM_TEAM))); c->teamLdsSet = 1; }
-    hipLaunchKernelGGL(hm355_ctu_team_kernel, dim3(L.grid), dim3(64 * waves), lds, L.stream, (const Params *)L.dP, (const WorkItem *)L.dItems, total, L.dSched, c->epoch);
+    hipLaunchKernelGGL(hm355_ctu_team_kernel, dim3(plan.teams), dim3(64 * waves), lds, L.stream, (const Params *)L.dP, (const WorkItem *)L.dItems, total, L.dSched, c->epoch);
   } else {
-    L.grid = total < (int)wsCount ? total : (int)wsCount;
-    // A caller that keeps `share` launches in flight (hm355_set_lane_share): each launch only takes its share of the searches the device can hold --
-    // a persistent workgroup that waits for a neighbouring CTU keeps its place on the CU, so a launch sized for the whole device would lock the
-    // others out until its tickets run out, and the launches would run one after the other
-    if (c->laneShare > 1) { const int cap = (int)(3072 * 5 / (4 * c->laneShare)); if (L.grid > cap) L.grid = cap; }
-    // workgroups of HM_CTU_WAVES independent searches (wavefronts); a search's workspace is blockIdx * HM_CTU_WAVES + wave < wsCount
-    int groups = (L.grid + HM_CTU_WAVES - 1) / HM_CTU_WAVES;
-    if (groups > (int)(wsCount / HM_CTU_WAVES)) groups = (int)(wsCount / HM_CTU_WAVES);
-    L.grid = groups * HM_CTU_WAVES;
-    hipLaunchKernelGGL(hm355_ctu_kernel, dim3(groups), dim3(64 * HM_CTU_WAVES), 0, L.stream, (const Params *)L.dP, (const WorkItem *)L.dItems, total, L.dSched, c->epoch);
+    if (plan.groups < 1) return fail(c, HM355_ERR_DEVICE, "hm355: a search launch without a workgroup");
+    hipLaunchKernelGGL(hm355_ctu_kernel, dim3(plan.groups), dim3(64 * HM_CTU_WAVES), 0, L.stream, (const Params *)L.dP, (const WorkItem *)L.dItems, total, L.dSched, c->epoch);
   }
   HM_CHECK(c, hipGetLastError());
+  if (l == 0 && !L.inFixup) {   // hm355_last_launch_shape: the main launch of the call, not the one-slot launches of dqp_verify_rows
+    c->lastShape.kernel = plan.useTeam; c->lastShape.waves = plan.useTeam ? waves : HM_CTU_WAVES; c->lastShape.few_waves = fewWaves;
+    c->lastShape.workgroups = plan.useTeam ? plan.teams : plan.groups; c->lastShape.tickets = total;
+  }
   HM_CHECK(c, hipEventRecord(L.ev1, L.stream));
   L.busy = 1;
   return HM355_OK;
@@ -990,6 +961,12 @@ extern "C" int hm355_last_run_info(const hm355_ctx *c, double *kernel_ms, int *l
   if (!c) return HM355_ERR_ARG;
   if (kernel_ms) *kernel_ms = c->lastKernelMs;
   if (launches) *launches = c->lastLaunches;
+  return HM355_OK;
+}
+extern "C" int hm355_last_launch_shape(const hm355_ctx *c, hm355_launch_shape *out)
+{
+  if (!c || !out) return HM355_ERR_ARG;
+  *out = c->lastShape;
   return HM355_OK;
 }
 

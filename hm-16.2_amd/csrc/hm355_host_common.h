@@ -128,3 +128,79 @@ static inline void hm355_build_schedule(int wCtu, int hCtu, int wpp, int nFrames
   }
   stepStart.push_back((int)items.size());
 }
+
+// ---- the shape of a search launch (run_begin / lane_init of hm355.hip): pure integer arithmetic, so that tests/hostsim/hostsim_plan.cpp can sweep it ----
+// needs HM_CTU_WAVES (hm355_core.h), HM_TEAM and HM_TEAM_I (hm355_team.h): both users include hm355_core.h first
+#define HM_WS_MAX 3072   /* 12 searches per CU x 256 CUs is the most that can be resident */
+// the widest step of the dependency schedule: as many CTUs of `frames` pictures as can ever be ready at once
+static inline int hm355_max_items_per_step(int wCtu, int hCtu, int wpp, int frames)
+{
+  if (!wpp) return frames;
+  int best = 0;
+  for (int s = 0; s < wCtu + 2 * (hCtu - 1); s++) { int c = 0; for (int y = 0; y < hCtu; y++) { int x = s - 2 * y; if (x >= 0 && x < wCtu) c++; } if (c > best) best = c; }
+  return best * frames;
+}
+// scratch areas (WorkSpace) of a lane: one per search its grid can hold -- a small batch runs as teams of HM_TEAM wavefronts per CTU; never fewer
+// than one workgroup of hm355_ctu_kernel needs (a one-CTU picture with max_batch 1 has 9 team workspaces, and a launch of it that may not use
+// teams -- a P / B slice with a fast-decision switch on, HM355_TEAM=0 -- used to get a grid of 0 workgroups)
+static inline long long hm355_ws_count(int numCtus, int maxBatch)
+{
+  long long n = (long long)numCtus * maxBatch * HM_TEAM;
+  if (n > HM_WS_MAX) n = HM_WS_MAX;
+  if (n < HM_CTU_WAVES) n = HM_CTU_WAVES;
+  return n;
+}
+struct hm355_launch_plan {
+  long long wsCount, parallel; int total;   // workspaces of the lane; CTUs the launch can offer at a time (estimate); tickets
+  int fewWaves;                             // Params::fewWaves
+  int teamWanted, waves, want;              // before the capacity is known: team kernel chosen, wavefronts per team, teams asked for (0: no team)
+  int useTeam, teams;                       // the launch: hm355_ctu_team_kernel with `teams` workgroups of `waves` wavefronts ...
+  int grid, groups;                         // ... or hm355_ctu_kernel with `groups` workgroups of HM_CTU_WAVES searches (grid = groups * HM_CTU_WAVES)
+};
+// n pictures of wCtu x hCtu CTUs, CTUs [ctu0, ctu1] of each, on a context created with max_batch and WaveFrontSynchro = wpp.  anyInter: a P / B slice
+// among them; fast: esd | cfm << 1 | ecu << 2; envTeam: HM355_TEAM (-1 unset, 0, 1); envTeamWaves: HM355_TEAM_WAVES (0 unset); laneShare:
+// hm355_set_lane_share; teamCap: teams the lane's reconstruction windows exist for (the caller grows them to `want` and plans again).
+static inline hm355_launch_plan hm355_plan_launch(int wCtu, int hCtu, int wpp, int maxBatch, int n, int ctu0, int ctu1, int anyInter, int fast,
+                                                  int envTeam, int envTeamWaves, int laneShare, long long teamCap)
+{
+  hm355_launch_plan p; memset(&p, 0, sizeof(p));
+  p.wsCount = hm355_ws_count(wCtu * hCtu, maxBatch);
+  p.total = n * (ctu1 - ctu0 + 1);
+  // A WPP picture offers about 16 CTUs at a time (one when the CABAC state chains through all of them).  A launch that cannot keep ~5
+  // one-wavefront searches per CU busy prefers the shortest dependency chain over the fewest instructions (fewWaves); one that cannot
+  // even give every CU two searches runs as teams of HM_TEAM wavefronts per CTU (HM355_TEAM=0 / 1 overrides for A/B runs).
+  // P / B slices: a team (nine wavefronts, one team per CU) takes a one-stream picture through 3x faster than one wavefront per CTU, and 256 teams together do about half of
+  // what 2,816 one-wavefront searches do: measured on 1080p low-delay P streams with WaveFrontSynchro (CTU/s, one wavefront / teams): 32 streams
+  // 798 / 1,556, 64: 1,538 / 2,356, 128: 2,862 / 2,944 -- teams up to 96 streams (1,024 when every stream is one serial chain of CTUs).
+  p.parallel = (long long)n * (wpp ? 16 : 1);
+  p.fewWaves = p.parallel < 1280 ? 1 : 0;
+  int useTeam = (anyInter ? (wpp ? n <= 96 : n <= 1024) : p.parallel <= 512) && p.wsCount >= HM_TEAM;
+  if (envTeam == 0) useTeam = 0;
+  if (envTeam == 1 && p.wsCount >= HM_TEAM) useTeam = 1;
+  // hm355_set_fast_decisions: the team protocol starts sub-CUs and partner candidates speculatively, which is not valid once candidates or
+  // sub-CUs may be cut short -- a P / B launch with any of the switches on is searched by one wavefront per CTU, whatever HM355_TEAM says
+  if (anyInter && fast) useTeam = 0;
+  p.waves = anyInter ? HM_TEAM : HM_TEAM_I;   // P / B slices: every chain of candidates on two or three wavefronts (hm355_team.h)
+  if (envTeamWaves == HM_TEAM_I) p.waves = HM_TEAM_I;   // A/B runs (five-wavefront teams on P streams: 1,021 / 1,529 / 1,871 CTU/s in the table above)
+  p.teamWanted = useTeam;
+  if (useTeam) {
+    // as many teams as CTUs can ever be ready at once (the wavefront's widest step), a few more so that a finished team finds the next ticket taken
+    const int rows = ctu1 / wCtu - ctu0 / wCtu + 1;
+    long long want = (long long)hm355_max_items_per_step(wCtu, rows < hCtu ? rows : hCtu, wpp, n) + 2;
+    if (want > p.total) want = p.total; if (want > 512) want = 512; if (want > p.wsCount / p.waves) want = p.wsCount / p.waves;
+    p.want = (int)want;
+    p.teams = (int)(want < teamCap ? want : teamCap);   // without windows (teamCap 0) the launch runs without teams
+  }
+  if (useTeam && p.teams > 0) { p.useTeam = 1; p.grid = p.teams; return p; }
+  p.teams = 0;
+  p.grid = p.total < (int)p.wsCount ? p.total : (int)p.wsCount;
+  // A caller that keeps `share` launches in flight (hm355_set_lane_share): each launch only takes its share of the searches the device can hold --
+  // a persistent workgroup that waits for a neighbouring CTU keeps its place on the CU, so a launch sized for the whole device would lock the
+  // others out until its tickets run out, and the launches would run one after the other
+  if (laneShare > 1) { const int cap = HM_WS_MAX * 5 / (4 * laneShare); if (p.grid > cap) p.grid = cap; }
+  // workgroups of HM_CTU_WAVES independent searches (wavefronts); a search's workspace is blockIdx * HM_CTU_WAVES + wave < wsCount
+  p.groups = (p.grid + HM_CTU_WAVES - 1) / HM_CTU_WAVES;
+  if (p.groups > (int)(p.wsCount / HM_CTU_WAVES)) p.groups = (int)(p.wsCount / HM_CTU_WAVES);
+  p.grid = p.groups * HM_CTU_WAVES;
+  return p;
+}

@@ -32,8 +32,7 @@
 //     a sub-CU was sensitive, the four sub-CUs are searched again with the part size known -- nothing outside the CU has seen them yet.
 #pragma once
 
-#define HM_TEAM 9                      /* wavefronts (and workspaces) of a team in a launch with P / B slices */
-#define HM_TEAM_I 5                    /* ... in a launch of I slices only: waves 0..4 */
+// HM_TEAM (9) / HM_TEAM_I (5), the wavefronts of a team: hm355_types.h (the launch plan of hm355_host_common.h needs them without this file)
 #define HM_TEAM_HELPERS 4              /* waves 1..4 own a reconstruction window (they evaluate intra candidates) */
 #define HM_TEAM_TIMEOUT_TICKS (20ull * 100000000ull)   /* 20 s of the 100 MHz wall clock: a team member that never answers abandons the launch */
 // wave 0: main;  1 + d: the unsplit CU of depth d = 0, 1, 2;  4: I slice: the 2Nx2N candidate of an 8x8 CU, P / B slice: the main wavefront's partner

@@ -56,6 +56,9 @@ struct InterPic {
 // planes of one CTU-sized scratch picture: Y 64x64 at 0, Cb 32x32 at 4096, Cr 32x32 at 5120
 #define HM_PLANE_OFF(c) ((c) == 0 ? 0 : ((c) == 1 ? 4096 : 5120))
 #define HM_PLANE_STRIDE(c) ((c) == 0 ? 64 : 32)
+// wavefronts of a team searching one CTU (hm355_team.h)
+#define HM_TEAM 9                      /* wavefronts (and workspaces) of a team in a launch with P / B slices */
+#define HM_TEAM_I 5                    /* ... in a launch of I slices only: waves 0..4 */
 // coefficients of one CTU in the reference's packing: Y at 0 (z*16), Cb at 4096 (z*4), Cr at 5120 (z*4)
 #define HM_COEF_CTU 6144
 

@@ -36,6 +36,10 @@ class SliceStats(C.Structure):
     _fields_ = [("pic_total_bits", C.c_uint64), ("pic_rd_cost", C.c_double), ("pic_dist", C.c_uint64)]
 
 
+class LaunchShape(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("waves", C.c_int32), ("few_waves", C.c_int32), ("workgroups", C.c_int32), ("tickets", C.c_int32)]
+
+
 CTU_DTYPE = np.dtype([("total_cost", "<f8"), ("total_bits", "<u4"), ("total_dist", "<u4"),
                       ("depth", "u1", 256), ("part_size", "u1", 256), ("pred_mode", "u1", 256),
                       ("intra_dir_luma", "u1", 256), ("intra_dir_chroma", "u1", 256), ("tr_idx", "u1", 256),
@@ -113,7 +117,7 @@ EXPORTS = ["hm355_build_id", "hm355_picture_stats_run", "hm355_picture_stats", "
            "hm355_compress_slice_inter", "hm355_compress_slices_inter", "hm355_deblock", "hm355_deblock_run", "hm355_ref_from_slot", "hm355_ref_release", "hm355_ref_bytes", "hm355_ref_export", "hm355_ref_import", "hm355_sao_run",
            "hm355_num_substreams", "hm355_encode_slices_run", "hm355_encode_slice",
            "hm355_upload_file_frames", "hm355_download_file_frames", "hm355_download_org",
-           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_dist_batch",
+           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_last_launch_shape", "hm355_dist_batch",
            "hm355_transform_batch"]
 
 
@@ -156,7 +160,8 @@ def load_library(path=LIB_PATH):
     lib.hm355_boundary_bytes.restype = C.c_size_t
     lib.hm355_export_boundary.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.hm355_import_boundary.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    lib.hm355_last_run_info.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    lib.hm355_last_launch_shape.argtypes = [C.c_void_p, C.POINTER(LaunchShape)]
+    lib.hm355_last_run_info.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]     # after its neighbour: HM355_OLD_LIB_OK makes a missing export an alias of this one
     lib.hm355_compress_slice.argtypes = [C.c_void_p, C.POINTER(SliceDesc), C.POINTER(Planes), C.POINTER(Planes), C.c_void_p,
                                          C.POINTER(SliceStats)]
     lib.hm355_compress_slice_inter.argtypes = [C.c_void_p, C.POINTER(InterSliceDesc), C.POINTER(Planes), C.POINTER(Planes), C.c_void_p,
@@ -336,6 +341,13 @@ class Encoder:
         ms, launches = C.c_double(), C.c_int()
         self.lib.hm355_last_run_info(self.h_, C.byref(ms), C.byref(launches))
         return ms.value, launches.value
+
+    def last_launch_shape(self):
+        """hm355_last_launch_shape -> dict(kernel "search12" | "team", waves, few_waves, workgroups, tickets) of the last search launch on lane 0
+        (the main launch of the call, not the rows a cu_qp_delta search repeats afterwards)"""
+        s = LaunchShape()
+        self._check(self.lib.hm355_last_launch_shape(self.h_, C.byref(s)), "hm355_last_launch_shape")
+        return dict(kernel="team" if s.kernel else "search12", waves=s.waves, few_waves=s.few_waves, workgroups=s.workgroups, tickets=s.tickets)
 
     def set_dqp(self, slot, ctu_qp=None, dqp_flag_in=0, use_dqp=1):
         """hm355_set_dqp: the following searches / deblocking / bitstream pass of the slot run with cu_qp_delta; ctu_qp int8 [numCtus] or None"""

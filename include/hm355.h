@@ -320,6 +320,17 @@ int hm355_import_boundary(hm355_ctx *ctx, int slot, int row, const void *buf);
 /* kernel time of the last hm355_run in milliseconds, measured with HIP events on the launch stream,
  * and the number of kernel launches it took */
 int hm355_last_run_info(const hm355_ctx *ctx, double *kernel_ms, int *launches);
+/* The shape of the last search launch on lane 0 (hm355_run, hm355_run_rows, hm355_run_ctus, hm355_compress_slice(s)(_inter), hm355_run_begin with
+ * lane 0), for tests and tuning runs that must know which code path they measured.  It is the FIRST launch of the call: the one-slot launches
+ * with which a cu_qp_delta search under WaveFrontSynchro repeats rows afterwards do not replace it.  All zero before the first search. */
+typedef struct hm355_launch_shape {
+  int32_t kernel;      /* 0: one wavefront per CTU search, 12 searches per workgroup; 1: a team of wavefronts per CTU search */
+  int32_t waves;       /* wavefronts per workgroup: 12, or the wavefronts of a team (5: I slices, 9: P / B slices) */
+  int32_t few_waves;   /* 1: the launch cannot fill the device and runs the code path with the shortest dependency chain; 0: the one with the fewest instructions */
+  int32_t workgroups;  /* workgroups launched */
+  int32_t tickets;     /* CTU searches of the launch */
+} hm355_launch_shape;
+int hm355_last_launch_shape(const hm355_ctx *ctx, hm355_launch_shape *out);
 
 /* ---- distortion / transform primitives as batched kernels (TComRdCost.cpp:465-1606,
  *      TComTrQuant.cpp:836-935); used by the known-answer parity tests and micro-benchmarks ----

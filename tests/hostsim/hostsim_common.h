@@ -1,6 +1,7 @@
 // DEBUGGING AID, NOT PRODUCT: what the host twins (hostsim.cpp, hostsim_inter.cpp, hostsim_rc.cpp) share -- the kernel source compiled for the
 // host with one "lane", Params and FrameBuf set up as the library sets them up, planar YUV input, and the HMD1 dump of the oracle CLI.
 // Everything the twins and the library must agree on is not here but in hm355_host_common.h, which both call.
+// hostsim_plan.cpp includes this file only for that header (the launch plan): it runs nothing of the kernel source.
 #pragma once
 #define HM355_HOSTSIM 1
 #include "../../hm-16.2_amd/csrc/hm355_core.h"

@@ -454,14 +454,27 @@ def test_hip_bitstream_pass_batch_matches_oracle(built, hm, wpp):
 
 def test_hip_bitstream_pass_more_substreams_than_resident_workgroups(built, hm):
     """2,720 substreams (80 pictures of 2 x 34 CTUs, WPP) in one launch: more than the workgroups the GPU keeps resident (about 2,300), with
-    the WPP hand-off between the rows of every picture -- the ticket order of the kernel must drain them; every picture against the oracle"""
+    the WPP hand-off between the rows of every picture -- the ticket order of the kernel must drain them; every picture against the oracle.  The search that fills the slots is itself the largest launch
+    of the suite (5,440 tickets, 12-search kernel, fewWaves == 0): its copies must agree and picture 0 must equal the oracle's search."""
     import oracle
     w, h, bd, qp, n = 128, 2176, 8, 36, 80
     enc = hm.Encoder(w, h, bd, 1, max_batch=n)
     pics = [synth.frame(w, h, bd, i % 5, 900 + i % 5) for i in range(n)]
     res = enc.compress(pics, qp)
+    shape = enc.last_launch_shape()           # the search that filled the slots: 5,440 tickets on the 12-search kernel at fewWaves == 0
+    assert (shape["kernel"], shape["waves"], shape["few_waves"], shape["tickets"]) == ("search12", 12, 0, n * 68) and shape["tickets"] > 12 * shape["workgroups"] >= 12, shape
     got = enc.encode_slices_run([dict(slice_type=2, qp=qp)] * n)
     enc.close()
+    # the search results the bitstream pass ran on: the 16 copies of each of the five pictures are equal, picture 0 equals the oracle's search
+    for i in range(5, n):
+        common.assert_ctus_equal(res[i][1], res[i % 5][1], f"search of picture {i} vs picture {i % 5}")
+        for k in range(3):
+            assert np.array_equal(res[i][0][k], res[i % 5][0][k]), f"picture {i} vs picture {i % 5}: reconstruction plane {k}"
+        assert res[i][2] == res[i % 5][2]
+    want_rec, want_ctus = oracle.compress(pics[0], bd, qp, 1)
+    common.assert_ctus_equal(res[0][1], want_ctus, "search of picture 0 vs the oracle")
+    for k in range(3):
+        assert np.array_equal(res[0][0][k], want_rec[k]), f"picture 0: reconstruction plane {k} differs from the oracle"
     want = {}
     for i in range(n):
         if i % 5 not in want:
