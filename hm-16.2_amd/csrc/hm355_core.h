@@ -368,7 +368,6 @@ struct Shared {
       uint8_t flags[72];
       RqtFrame rqt[4]; uint32_t rqtRetDist[5], rqtRetBits[5]; double rqtRetCost[5];
       int32_t rdModeList[12];
-      uint8_t splitCbf[5][2];
       uint32_t outDistY;
       uint32_t satd[36];               // SATD of the 35 intra modes of the PU under test
       int32_t mpmNum, mpmPreds[3];     // most-probable-mode list of the PU under test (same for all its candidates)
@@ -729,6 +728,20 @@ HM_DEV inline TU tu_child(const TU *p, int section, int processLast)
   }
   return t;
 }
+// Pre-order walk of a residual quadtree on an explicit stack in LDS (no device recursion, no private-memory traffic).
+// enter(t) handles a node and says whether its four children follow; leave(t) runs when the fourth has returned.
+template <class Enter, class Leave> HM_FINL void tu_walk(TuWalk &w, const TU *root, int processLast, Enter enter, Leave leave)
+{
+  w.node[0] = *root; w.next[0] = -1; w.sp = 0;
+  while (w.sp >= 0) {
+    TU *t = &w.node[w.sp];
+    if (w.next[w.sp] < 0) { if (!enter((const TU *)t)) { w.sp--; continue; } w.next[w.sp] = 0; }
+    if (w.next[w.sp] == 4) { leave((const TU *)t); w.sp--; continue; }
+    const int s = w.next[w.sp]++;
+    w.node[w.sp + 1] = tu_child(t, s, processLast); w.next[w.sp + 1] = -1; w.sp++;
+  }
+}
+template <class Enter> HM_FINL void tu_walk(TuWalk &w, const TU *root, int processLast, Enter enter) { tu_walk(w, root, processLast, enter, [](const TU *) {}); }
 
 // ------------------------------------------------------------------------------------------------
 // neighbour helpers
@@ -1809,67 +1822,53 @@ HM_DEV inline int tr_min_size_in_cu(int cuLog2, int nxn)
   return v > 5 ? 5 : v;
 }
 // whether a transform_split flag is coded at this node (TEncSearch.cpp:869-888 / TEncEntropy.cpp:258-291)
-HM_DEV inline int codes_subdiv_flag(const CtuMeta *m, const TU *t)
+HM_DEV inline int codes_subdiv_flag(const CtuMeta *m, const TU *t, int intra)
 {
-  const int nxn = m->part[t->cuZ] == SIZE_NxN;
+  const int nxn = intra && m->part[t->cuZ] == SIZE_NxN;
   if (nxn && t->trDepth == 0) return 0;
   if (t->log2 > 5) return 0;
   if (t->log2 == 2) return 0;
   if (t->log2 == tr_min_size_in_cu(6 - t->cuDepth, nxn)) return 0;
   return 1;
 }
-
-// Pre-order walk of the residual quadtree with an explicit stack (no device recursion).
-// The callbacks of the reference's recursive functions become phases of one loop.
-HM_DEV inline void walk_begin(TuWalk *w, const TU *root) { w->node[0] = *root; w->next[0] = -1; w->sp = 0; }
+// cbf_cb / cbf_cr of a node: at the root, below it where the parent has one (TEncSearch.cpp:890-907 / TEncEntropy.cpp:293-318)
+template <class C> HM_DEV inline void code_chroma_cbfs(Shared *e, C *c, const TU *t, int subdiv)
+{
+  const CtuMeta *m = (&e->meta); const int z = t->cuZ + t->relZ;
+  for (int comp = 1; comp < 3; comp++)
+    if (t->trDepth == 0 || (t->cCodeAll && ((m->cbf[comp][z] >> (t->trDepth - 1)) & 1))) code_qt_cbf(e, c, t, comp, subdiv == 0);
+}
+// one component of a leaf, if it has a coded block (TEncEntropy::encodeCoeffNxN, TEncEntropy.cpp:683); planes: the CTU arrays or a QT layer
+template <class C> HM_DEV inline void code_tu_coeff(Shared *e, C *c, const TU *t, int comp, const TCoeff *planes, int intra)
+{
+  const CtuMeta *m = (&e->meta); const int z = t->cuZ + t->relZ;
+  if ((comp && !t->cW) || !((m->cbf[comp][z] >> t->trDepth) & 1)) return;
+  const int n = comp ? t->cW : (1 << t->log2), zc = t->cuZ + (comp ? t->cRelZ : t->relZ);
+  const TCoeff *coef = planes + HM_PLANE_OFF(comp) + (comp ? t->cOff : z * 16);
+  code_coeff_nxn(e, c, coef, n, comp, intra ? coef_scan_idx(m, zc, n, comp) : SCAN_DIAG, m->ts[comp][zc]);
+}
 
 // xEncSubdivCbfQT, TEncSearch.cpp:856-921
 template <class C> HM_DEV inline void enc_subdiv_cbf_qt(Shared *e, C *c, const TU *root, int bLuma, int bChroma)
 {
   const CtuMeta *m = (&e->meta);
-  TuWalk &w = e->walkInner; walk_begin(&w, root);
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
-    const int z = t->cuZ + t->relZ;
-    const int subdiv = m->tr[z] > t->trDepth;
-    if (w.next[w.sp] < 0) { // first visit
-      if (bLuma && codes_subdiv_flag(m, t)) enc_bin(e, c, C_SUBDIV + (5 - t->log2), subdiv);
-      if (bChroma)
-        for (int comp = 1; comp < 3; comp++)
-          if (t->cCodeAll && (t->trDepth == 0 || ((m->cbf[comp][z] >> (t->trDepth - 1)) & 1)))
-            code_qt_cbf(e, c, t, comp, subdiv == 0);
-      if (!subdiv) { if (bLuma) code_qt_cbf(e, c, t, 0, 1); w.sp--; continue; }
-      w.next[w.sp] = 0;
-    }
-    if (w.next[w.sp] == 4) { w.sp--; continue; }
-    const int s = w.next[w.sp]++;
-    w.node[w.sp + 1] = tu_child(t, s, 0); w.next[w.sp + 1] = -1; w.sp++;
-  }
+  tu_walk(e->walkInner, root, 0, [&](const TU *t) {
+    const int subdiv = m->tr[t->cuZ + t->relZ] > t->trDepth;
+    if (bLuma && codes_subdiv_flag(m, t, 1)) enc_bin(e, c, C_SUBDIV + (5 - t->log2), subdiv);
+    if (bChroma) code_chroma_cbfs(e, c, t, subdiv);
+    if (!subdiv && bLuma) code_qt_cbf(e, c, t, 0, 1);
+    return subdiv;
+  });
 }
 // xEncCoeffQT, TEncSearch.cpp:926-960 (coefficients from the QT layer buffers)
 HM_DEV inline void enc_coeff_qt(Shared *e, const TU *root, int comp)
 {
   const CtuMeta *m = (&e->meta);
-  TuWalk &w = e->walkInner; walk_begin(&w, root);
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
-    const int z = t->cuZ + t->relZ;
-    if (m->tr[z] > t->trDepth) {
-      if (w.next[w.sp] < 0) w.next[w.sp] = 0;
-      if (w.next[w.sp] == 4) { w.sp--; continue; }
-      const int s = w.next[w.sp]++;
-      w.node[w.sp + 1] = tu_child(t, s, 0); w.next[w.sp + 1] = -1; w.sp++;
-      continue;
-    }
-    if (!(comp && !t->cW) && ((m->cbf[comp][z] >> t->trDepth) & 1)) {   // TEncEntropy::encodeCoeffNxN, TEncEntropy.cpp:683
-      const int layer = 5 - t->log2;
-      const int n = comp ? t->cW : (1 << t->log2);
-      const int zc = t->cuZ + (comp ? t->cRelZ : t->relZ);
-      const TCoeff *coef = e->ws->qtCoef[layer] + HM_PLANE_OFF(comp) + (comp ? t->cOff : z * 16);
-      code_coeff_nxn(e, &e->cur, coef, n, comp, coef_scan_idx(m, zc, n, comp), m->ts[comp][zc]);
-    }
-    w.sp--;
-  }
+  tu_walk(e->walkInner, root, 0, [&](const TU *t) {
+    if (m->tr[t->cuZ + t->relZ] > t->trDepth) return 1;
+    code_tu_coeff(e, &e->cur, t, comp, e->ws->qtCoef[5 - t->log2], 1);
+    return 0;
+  });
 }
 // xEncIntraHeader, TEncSearch.cpp:965-1032 (I slice, no PCM)
 template <class C> HM_DEV inline void enc_intra_header(Shared *e, C *c, const TU *t, int bLuma, int bChroma)
@@ -2357,50 +2356,36 @@ HM_DEV HM_NOINLINE uint32_t recur_intra_chroma_coding_qt(Shared *e, TU rootv)
   const TU *root = &rootv;
   CtuMeta *m = (&e->meta);
   uint32_t dist = 0;
-  TuWalk &w = e->walkOuter; walk_begin(&w, root);
-  uint8_t (*splitCbf)[2] = e->splitCbf;
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
-    const int z = t->cuZ + t->relZ;
-    if (m->tr[z] == t->trDepth) { if (t->cW) dist += chroma_tu(e, t); w.sp--; continue; }
-    if (w.next[w.sp] < 0) { w.next[w.sp] = 0; splitCbf[w.sp][0] = splitCbf[w.sp][1] = 0; }
-    if (w.next[w.sp] > 0) { // a child just returned
-      const TU ch = tu_child(t, w.next[w.sp] - 1, 0);
-      for (int c = 1; c < 3; c++) splitCbf[w.sp][c - 1] |= (m->cbf[c][ch.cuZ + ch.relZ] >> ch.trDepth) & 1;
-    }
-    if (w.next[w.sp] == 4) {
-      HM_PAR_FOR(o, t->parts) for (int c = 1; c < 3; c++) if (splitCbf[w.sp][c - 1]) m->cbf[c][z + o] |= (uint8_t)(1 << t->trDepth);
+  tu_walk(e->walkOuter, root, 0,
+    [&](const TU *t) {
+      if (m->tr[t->cuZ + t->relZ] != t->trDepth) return 1;
+      if (t->cW) dist += chroma_tu(e, t);
+      return 0;
+    },
+    [&](const TU *t) {   // a split node has a chroma cbf at its depth when one of its children has: a child writes only its own range (of 4x4 luma blocks the first writes all four parts, the others carry no chroma)
+      const int z = t->cuZ + t->relZ, q = t->parts >> 2;
+      int any = 0;
+      for (int c = 1; c < 3; c++) for (int s = 0; s < 4; s++) any |= ((m->cbf[c][z + s * q] >> (t->trDepth + 1)) & 1) << c;
+      HM_PAR_FOR(o, t->parts) for (int c = 1; c < 3; c++) if ((any >> c) & 1) m->cbf[c][z + o] |= (uint8_t)(1 << t->trDepth);
       HM_SYNC();
-      w.sp--; continue;
-    }
-    const int s = w.next[w.sp]++;
-    w.node[w.sp + 1] = tu_child(t, s, 0); w.next[w.sp + 1] = -1; w.sp++;
-  }
+    });
   return dist;
 }
 // xSetIntraResultChromaQT, TEncSearch.cpp:2150-2200: visit the chroma leaves
 HM_DEV inline void set_intra_result_chroma_qt(Shared *e, const TU *root)
 {
   const CtuMeta *m = (&e->meta);
-  TuWalk &w = e->walkOuter; walk_begin(&w, root);
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
-    const int z = t->cuZ + t->relZ;
-    if (!t->cW) { w.sp--; continue; }
-    if (m->tr[z] == t->trDepth) {
-      const int n = t->cW, layer = 5 - t->log2;
-      for (int c = 1; c < 3; c++) {
-        const int po = HM_PLANE_OFF(c);
-        par_copy32(e->cc + po + t->cOff, e->ws->qtCoef[layer] + po + t->cOff, n * n);
-        par_copy_blk(e->ws->reco + po + t->cy * 32 + t->cx, 32, e->ws->qtRec[layer] + po + t->cy * 32 + t->cx, 32, n);
-      }
-      w.sp--; continue;
+  tu_walk(e->walkOuter, root, 0, [&](const TU *t) {
+    if (!t->cW) return 0;
+    if (m->tr[t->cuZ + t->relZ] != t->trDepth) return 1;
+    const int n = t->cW, layer = 5 - t->log2;
+    for (int c = 1; c < 3; c++) {
+      const int po = HM_PLANE_OFF(c);
+      par_copy32(e->cc + po + t->cOff, e->ws->qtCoef[layer] + po + t->cOff, n * n);
+      par_copy_blk(e->ws->reco + po + t->cy * 32 + t->cx, 32, e->ws->qtRec[layer] + po + t->cy * 32 + t->cx, 32, n);
     }
-    if (w.next[w.sp] < 0) w.next[w.sp] = 0;
-    if (w.next[w.sp] == 4) { w.sp--; continue; }
-    const int s = w.next[w.sp]++;
-    w.node[w.sp + 1] = tu_child(t, s, 0); w.next[w.sp + 1] = -1; w.sp++;
-  }
+    return 0;
+  });
 }
 HM_DEV HM_NOINLINE uint32_t est_intra_pred_chroma_qt(Shared *e, int cuZ, int cuDepth)
 {
@@ -2510,8 +2495,23 @@ HM_DEV inline int first_coded_cu(const Shared *e)
 }
 
 // ------------------------------------------------------------------------------------------------
-// final syntax of a CU (TEncEntropy::xEncodeTransform, TEncEntropy.cpp:222-412)
+// final syntax of a CU
 // ------------------------------------------------------------------------------------------------
+// TEncEntropy::xEncodeTransform, TEncEntropy.cpp:222-412: the transform tree of a finished CU, intra or inter (coefficients from the CTU arrays)
+template <class C> HM_DEV inline void encode_transform(Shared *e, C *c, const TU *root, int intra, int codeDqp)
+{
+  const CtuMeta *m = (&e->meta);
+  tu_walk(e->walkOuter, root, 1, [&](const TU *t) {
+    const int z = t->cuZ + t->relZ, subdiv = m->tr[z] > t->trDepth;
+    if (codes_subdiv_flag(m, t, intra)) enc_bin(e, c, C_SUBDIV + (5 - t->log2), subdiv);
+    code_chroma_cbfs(e, c, t, subdiv);
+    if (subdiv) return 1;
+    if (intra || t->trDepth || ((m->cbf[1][z] | m->cbf[2][z]) & 1)) code_qt_cbf(e, c, t, 0, 1);            // the luma cbf of an inter root without chroma cbfs is inferred
+    if (codeDqp && (((m->cbf[0][z] | m->cbf[1][z] | m->cbf[2][z]) >> t->trDepth) & 1)) code_dqp_if_due(e, c);   // bHaveACodedBlock, TEncEntropy.cpp:343
+    for (int comp = 0; comp < 3; comp++) code_tu_coeff(e, c, t, comp, e->cc, intra);
+    return 0;
+  });
+}
 template <class C> HM_DEV HM_NOINLINE void encode_cu_syntax(Shared *e, C *c, int cuZ, int cuDepth)
 {
   HM_ENTRY(e); cuZ = HM_UNI(cuZ); cuDepth = HM_UNI(cuDepth); c = hm_uni_ptr(c); HM_ASSUME_LDS(c); // CU-level syntax shared by xCheckRDCostIntra (TEncCu.cpp:1601-1626) and xEncodeCU (:1246-1288), I slice
@@ -2527,36 +2527,7 @@ template <class C> HM_DEV HM_NOINLINE void encode_cu_syntax(Shared *e, C *c, int
   if (EngOf<C>::REAL) { e->prof[PR_SAVE] += __builtin_readcyclecounter() - profDir0; e->profCnt[PR_SAVE] += 1; }
 #endif
   const TU root = tu_root(e, cuZ, cuDepth);
-  TuWalk &w = e->walkOuter; walk_begin(&w, &root);
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
-    const int z = t->cuZ + t->relZ;
-    const int subdiv = m->tr[z] > t->trDepth;
-    if (w.next[w.sp] < 0) {
-      if (codes_subdiv_flag(m, t)) enc_bin(e, c, C_SUBDIV + (5 - t->log2), subdiv);
-      const int first = t->trDepth == 0;
-      for (int comp = 1; comp < 3; comp++)
-        if (first || t->cCodeAll)
-          if (first || ((m->cbf[comp][z] >> (t->trDepth - 1)) & 1)) code_qt_cbf(e, c, t, comp, subdiv == 0);
-      if (!subdiv) {
-        code_qt_cbf(e, c, t, 0, 1);
-        if (((m->cbf[0][z] | m->cbf[1][z] | m->cbf[2][z]) >> t->trDepth) & 1) code_dqp_if_due(e, c);      // bHaveACodedBlock, TEncEntropy.cpp:343
-        for (int comp = 0; comp < 3; comp++) {
-          if (comp && !t->cW) continue;
-          if (!((m->cbf[comp][z] >> t->trDepth) & 1)) continue;
-          const int n = comp ? t->cW : (1 << t->log2);
-          const int zc = t->cuZ + (comp ? t->cRelZ : t->relZ);
-          const TCoeff *coef = e->cc + HM_PLANE_OFF(comp) + (comp ? t->cOff : z * 16);
-          code_coeff_nxn(e, c, coef, n, comp, coef_scan_idx(m, zc, n, comp), m->ts[comp][zc]);
-        }
-        w.sp--; continue;
-      }
-      w.next[w.sp] = 0;
-    }
-    if (w.next[w.sp] == 4) { w.sp--; continue; }
-    const int s = w.next[w.sp]++;
-    w.node[w.sp + 1] = tu_child(t, s, 1); w.next[w.sp + 1] = -1; w.sp++;
-  }
+  encode_transform(e, c, &root, 1, 1);
 }
 
 // ------------------------------------------------------------------------------------------------

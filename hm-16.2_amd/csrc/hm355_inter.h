@@ -1136,44 +1136,6 @@ template <class C> HM_DEV inline void code_pu_wise(Shared *e, C *c, int cuZ, int
 }
 HM_DEV inline int qt_root_cbf(const CtuMeta *m, int z) { return (m->cbf[0][z] & 1) || (m->cbf[1][z] & 1) || (m->cbf[2][z] & 1); }
 
-// TEncEntropy::xEncodeTransform :222-412 for an inter CU (coefficients from the CTU arrays)
-template <class C> HM_DEV inline void encode_transform_inter(Shared *e, C *c, const TU *root, int codeDqp)
-{
-  const CtuMeta *m = &e->meta;
-  TuWalk &w = e->walkOuter; walk_begin(&w, root);
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
-    const int z = t->cuZ + t->relZ;
-    const int subdiv = m->tr[z] > t->trDepth;
-    if (w.next[w.sp] < 0) {
-      if (t->log2 > 5) { }
-      else if (t->log2 == 2) { }
-      else if (t->log2 == tr_min_size_in_cu(6 - t->cuDepth, 0)) { }
-      else enc_bin(e, c, C_SUBDIV + (5 - t->log2), subdiv);
-      const int first = t->trDepth == 0;
-      for (int comp = 1; comp < 3; comp++)
-        if (first || t->cCodeAll)
-          if (first || ((m->cbf[comp][z] >> (t->trDepth - 1)) & 1)) code_qt_cbf(e, c, t, comp, subdiv == 0);
-      if (!subdiv) {
-        if (!(first && !(m->cbf[1][z] & 1) && !(m->cbf[2][z] & 1))) code_qt_cbf(e, c, t, 0, 1);
-        if (codeDqp && (((m->cbf[0][z] | m->cbf[1][z] | m->cbf[2][z]) >> t->trDepth) & 1)) code_dqp_if_due(e, c);
-        for (int comp = 0; comp < 3; comp++) {
-          if (comp && !t->cW) continue;
-          if (!((m->cbf[comp][z] >> t->trDepth) & 1)) continue;
-          const int n = comp ? t->cW : (1 << t->log2);
-          const int zc = t->cuZ + (comp ? t->cRelZ : t->relZ);
-          const TCoeff *coef = e->cc + HM_PLANE_OFF(comp) + (comp ? t->cOff : z * 16);
-          code_coeff_nxn(e, c, coef, n, comp, SCAN_DIAG, m->ts[comp][zc]);
-        }
-        w.sp--; continue;
-      }
-      w.next[w.sp] = 0;
-    }
-    if (w.next[w.sp] == 4) { w.sp--; continue; }
-    const int s = w.next[w.sp]++;
-    w.node[w.sp + 1] = tu_child(t, s, 1); w.next[w.sp + 1] = -1; w.sp++;
-  }
-}
 // the whole inter CU: xAddSymbolBitsInter :5517 (codeDqp 0: "Bool codeDeltaQp = false") and xEncodeCU :1246-1290 (codeDqp 1: TEncCu::m_bEncodeDQP decides)
 template <class C> HM_DEV HM_NOINLINE void encode_cu_syntax_inter(Shared *e, C *c, int cuZ, int cuDepth, int codeDqp)
 {
@@ -1187,7 +1149,7 @@ template <class C> HM_DEV HM_NOINLINE void encode_cu_syntax_inter(Shared *e, C *
   if (!(im->mrg[cuZ] && m->part[cuZ] == SIZE_2Nx2N)) enc_bin(e, c, C_ROOT_CBF, qt_root_cbf(m, cuZ));
   if (!qt_root_cbf(m, cuZ)) return;
   const TU root = tu_root(e, cuZ, cuDepth);
-  encode_transform_inter(e, c, &root, codeDqp);
+  encode_transform(e, c, &root, 0, codeDqp);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1196,64 +1158,36 @@ template <class C> HM_DEV HM_NOINLINE void encode_cu_syntax_inter(Shared *e, C *
 HM_DEV inline void encode_residual_qt(Shared *e, const TU *root, int comp /* 3 = flags pass */)
 {
   const CtuMeta *m = &e->meta;
-  TuWalk &w = e->walkInner; walk_begin(&w, root);
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
-    const int z = t->cuZ + t->relZ, trMode = m->tr[z], subdiv = t->trDepth != trMode;
-    if (w.next[w.sp] < 0) {
-      if (comp == 3) {
-        if (t->log2 <= 5 && t->log2 > tr_min_size_in_cu(6 - t->cuDepth, 0)) enc_bin(e, &e->cur, C_SUBDIV + (5 - t->log2), subdiv);
-        const int first = t->trDepth == 0;
-        for (int ch = 1; ch < 3; ch++)
-          if (first || t->cCodeAll)
-            if (first || ((m->cbf[ch][z] >> (t->trDepth - 1)) & 1)) code_qt_cbf(e, &e->cur, t, ch, !subdiv);
-        if (!subdiv) code_qt_cbf(e, &e->cur, t, 0, 1);
-      }
-      if (!subdiv) {
-        if (comp != 3 && !(comp && !t->cW)) {
-          const int zc = t->cuZ + (comp ? t->cRelZ : t->relZ);
-          if ((m->cbf[comp][z] >> trMode) & 1) {
-            const int n = comp ? t->cW : (1 << t->log2);
-            const TCoeff *coef = e->ws->qtCoef[5 - t->log2] + HM_PLANE_OFF(comp) + (comp ? t->cOff : z * 16);
-            code_coeff_nxn(e, &e->cur, coef, n, comp, SCAN_DIAG, m->ts[comp][zc]);
-          }
-        }
-        w.sp--; continue;
-      }
-      if (!(comp == 3 || ((m->cbf[comp][z] >> t->trDepth) & 1))) { w.sp--; continue; }
-      w.next[w.sp] = 0;
+  tu_walk(e->walkInner, root, 0, [&](const TU *t) {
+    const int z = t->cuZ + t->relZ, subdiv = t->trDepth != m->tr[z];
+    if (comp == 3) {
+      if (codes_subdiv_flag(m, t, 0)) enc_bin(e, &e->cur, C_SUBDIV + (5 - t->log2), subdiv);
+      code_chroma_cbfs(e, &e->cur, t, subdiv);
+      if (!subdiv) code_qt_cbf(e, &e->cur, t, 0, 1);
+      return subdiv;
     }
-    if (w.next[w.sp] == 4) { w.sp--; continue; }
-    const int s = w.next[w.sp]++;
-    w.node[w.sp + 1] = tu_child(t, s, 0); w.next[w.sp + 1] = -1; w.sp++;
-  }
+    if (subdiv) return (m->cbf[comp][z] >> t->trDepth) & 1;             // a subtree without a coded block of the component has nothing to code
+    code_tu_coeff(e, &e->cur, t, comp, e->ws->qtCoef[5 - t->log2], 0);
+    return 0;
+  });
 }
 HM_DEV inline void set_residual_qt_data(Shared *e, const TU *root, int spatial)
 {
   const CtuMeta *m = &e->meta;
-  TuWalk &w = e->walkInner; walk_begin(&w, root);
-  while (w.sp >= 0) {
-    TU *t = &w.node[w.sp];
+  tu_walk(e->walkInner, root, 0, [&](const TU *t) {
     const int z = t->cuZ + t->relZ;
-    if (w.next[w.sp] < 0) {
-      if (t->trDepth == m->tr[z]) {
-        const int layer = 5 - t->log2;
-        for (int comp = 0; comp < 3; comp++) {
-          if (comp && !t->cW) continue;
-          const int n = comp ? t->cW : (1 << t->log2), l2 = hm_log2(n), st = HM_PLANE_STRIDE(comp), po = HM_PLANE_OFF(comp), bx = comp ? t->cx : t->x, by = comp ? t->cy : t->y;
-          const int coded = (m->cbf[comp][t->cuZ + (comp ? t->cRelZ : t->relZ)] >> t->trDepth) & 1;      // an empty block: zeros (irq_check_full leaves its buffers as they were)
-          if (spatial) { HM_PAR_FOR(i, n * n) { const int y = i >> l2, x = i & (n - 1); e->ws->resiBest[po + (by + y) * st + bx + x] = coded ? e->ws->qtRec[layer][po + (by + y) * st + bx + x] : (Pel)0; } }
-          else { const int off = po + (comp ? t->cOff : z * 16); HM_PAR_FOR(i, n * n) e->cc[off + i] = coded ? e->ws->qtCoef[layer][off + i] : 0; }
-        }
-        HM_SYNC();
-        w.sp--; continue;
-      }
-      w.next[w.sp] = 0;
+    if (t->trDepth != m->tr[z]) return 1;
+    const int layer = 5 - t->log2;
+    for (int comp = 0; comp < 3; comp++) {
+      if (comp && !t->cW) continue;
+      const int n = comp ? t->cW : (1 << t->log2), l2 = hm_log2(n), st = HM_PLANE_STRIDE(comp), po = HM_PLANE_OFF(comp), bx = comp ? t->cx : t->x, by = comp ? t->cy : t->y;
+      const int coded = (m->cbf[comp][t->cuZ + (comp ? t->cRelZ : t->relZ)] >> t->trDepth) & 1;      // an empty block: zeros (irq_check_full leaves its buffers as they were)
+      if (spatial) { HM_PAR_FOR(i, n * n) { const int y = i >> l2, x = i & (n - 1); e->ws->resiBest[po + (by + y) * st + bx + x] = coded ? e->ws->qtRec[layer][po + (by + y) * st + bx + x] : (Pel)0; } }
+      else { const int off = po + (comp ? t->cOff : z * 16); HM_PAR_FOR(i, n * n) e->cc[off + i] = coded ? e->ws->qtCoef[layer][off + i] : 0; }
     }
-    if (w.next[w.sp] == 4) { w.sp--; continue; }
-    const int s = w.next[w.sp]++;
-    w.node[w.sp + 1] = tu_child(t, s, 0); w.next[w.sp + 1] = -1; w.sp++;
-  }
+    HM_SYNC();
+    return 0;
+  });
 }
 
 // full (unsplit) evaluation of one TU: every component, transform-skip trial for 4x4 blocks (:4725-5106)

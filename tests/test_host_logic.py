@@ -79,11 +79,13 @@ def test_schedule_respects_dependencies(wc, hc, wpp, carry):
     assert len(done) == 2 * wc * hc
 
 
-def test_hostsim_of_kernel_source_matches_reference_fixture(tmp_path):
+@pytest.mark.parametrize("name", ["small_128x128_10b_qp37", "wpp_416x240_10b_qp32", "c1_416x240_8b_qp32"])
+def test_hostsim_of_kernel_source_matches_reference_fixture(tmp_path, name):
     """The kernel source (hm355_core.h) compiled for the host with one lane, forwards and with every
-    lane-parallel loop reversed, reproduces the reference fixture.  Debugging aid: the GPU tests are the gate."""
+    lane-parallel loop reversed, reproduces the reference fixture (the two 416x240 ones hold transform trees of
+    depth 2, the small one stops at depth 1).  Debugging aid: the GPU tests are the gate."""
     import synth
-    cfg, frames = common.load_case("small_128x128_10b_qp37")
+    cfg, frames = common.load_case(name)
     yuv = tmp_path / "in.yuv"
     synth.write_yuv(str(yuv), cfg["width"], cfg["height"], cfg["bit_depth"], cfg["frames"], cfg["seed"])
     import gen_golden
