@@ -162,7 +162,7 @@ __device__ __forceinline__ double hm_readlane_d(double v, int i)
 
 // optional in-kernel cycle accounting (diagnostic build only: -DHM355_PROFILE, never in the product build)
 #if defined(HM355_PROFILE) && !defined(HM355_HOSTSIM)
-#define HM_PROF_N 44
+#define HM_PROF_N 45
 #define HM_PROF_BEGIN(e, id) const unsigned long long prof_t0_##id = __builtin_readcyclecounter()
 #define HM_PROF_END(e, id) do { (e)->prof[id] += __builtin_readcyclecounter() - prof_t0_##id; (e)->profCnt[id] += 1; } while (0)
 #else
@@ -170,7 +170,7 @@ __device__ __forceinline__ double hm_readlane_d(double v, int i)
 #define HM_PROF_END(e, id) ((void)0)
 #endif
 enum { PR_RDOQ = 0, PR_BITS, PR_ADI, PR_PRED, PR_FWD, PR_INV, PR_SATD35, PR_TUBLK, PR_SAVE, PR_CHROMA, PR_LUMA, PR_ENCCU, PR_TOTAL,
-       PR_S4L = 32, PR_S4C, PR_D0, PR_D1, PR_D2, PR_D3, PR_NXN, PR_S8L, PR_S4LEAF, PR_S4CLEAF, PR_S8C,
+       PR_S4L = 32, PR_S4C, PR_D0, PR_D1, PR_D2, PR_D3, PR_NXN, PR_S8L, PR_S4LEAF, PR_S4CLEAF, PR_S8C, PR_S16L = 44,
        PR_ME_INT = 16, PR_ME_FRAC, PR_AMVP, PR_MRG_EST, PR_MC, PR_IRQ, PR_IRES, PR_MRG2N, PR_INTERCU, PR_INTRA_IN_P, PR_IQ_FULL, PR_IQ_FWD, PR_IQ_RDOQ, PR_IQ_BITS, PR_IQ_INV, PR_IQ_ENC };
 
 #define HM_MAX_DOUBLE 1.7e+308
@@ -331,7 +331,11 @@ struct RefLds {
 #define HM_SLOT(d, ci) ((d) * CI_NUM + (ci) - ((d) == 4 ? 2 : 0))
 #define HM_NUM_SLOTS (4 * CI_NUM + 3)
 struct Team;                           // hm355_team.h: the wavefronts of one workgroup searching one CTU together (latency mode)
+#if defined(HM355_PROFILE) && !defined(HM355_HOSTSIM)
+#define HM_CTU_WAVES 11                 /* diagnostic build: the cycle counters of the searches take the LDS of the twelfth */
+#else
 #define HM_CTU_WAVES 12                 /* independent CTU searches (wavefronts) per workgroup of hm355_ctu_kernel: they share one LdsTables */
+#endif
 // read-only tables every CTU search of a workgroup shares (one copy per workgroup: the searches of a workgroup are independent wavefronts)
 struct LdsTables {
   int8_t tmat[32 * HM_TSTRIDE];        // 32-point transform matrix, padded rows
@@ -357,7 +361,7 @@ struct Shared {
   // results handed back by the big non-inlined stages (instead of pointers to private memory)
   double outCost; uint32_t outBits, outDist; double outRdCost;
   int32_t mpmZ;                        // the PU whose most-probable-mode list is tabulated below (-1: none)
-  int32_t s8Winner, s8Reuse;           // hm355_simt8.h: the first pass's winning candidate; set while its evaluation can stand in for the closing pass's unsplit 8x8 TU
+  int32_t s8Winner, s8Reuse;           // 8x8 and 16x16 PUs alike (hm355_simt8.h / hm355_simt16.h): the first pass's winning candidate (slot | place in the list << 8); set while its evaluation can stand in for the closing pass's unsplit TU
   // inter (P / B slice) state that outlives a stage
   InterMeta *im;                       // motion arrays of the CTU under search (HBM)
   uint32_t mcost; MvD mvPredictor; int32_t costScale;   // TComRdCost motion-cost state
@@ -412,7 +416,9 @@ __device__ inline void hm_trace(Shared *e, int tag, uint32_t a, uint32_t b, doub
 __shared__ Shared g_sh;                // the one wavefront of the secondary kernels' workgroups
 __shared__ Shared g_shs[HM_CTU_WAVES];  // the CTU searches of a workgroup of hm355_ctu_kernel
 #endif
-#if !defined(HM355_PROFILE)
+#if defined(HM355_PROFILE)
+static_assert(HM_CTU_WAVES * (sizeof(Shared) + 16) + sizeof(LdsTables) <= 163840, "the diagnostic build: one workgroup of HM_CTU_WAVES searches with their cycle counters in 160 KB of LDS");
+#else
 static_assert(HM_CTU_WAVES * (sizeof(Shared) + 16) + sizeof(LdsTables) <= 163840 / (12 / HM_CTU_WAVES) && sizeof(Shared) % 8 == 0, "two workgroups of HM_CTU_WAVES searches (+ work items, + the shared tables) per CU: 12 CTU searches in 160 KB of LDS");
 #endif
 static_assert(offsetof(Shared, bufA) % 8 == 0 && (16 * HM_TSTRIDE * 4) % 8 == 0, "the RDOQ cost array aliases the lower half of bufA as doubles");
@@ -2017,7 +2023,7 @@ HM_DEV inline void load_intra_result_qt(Shared *e, const TU *t, int comp)
 // ------------------------------------------------------------------------------------------------
 // returns distortion through *distY and adds the RD cost to *rdCost, exactly like the recursive reference
 HM_DEV HM_NOINLINE void simt4_luma_leaf(Shared *e, TU tv);      // hm355_simt4.h
-HM_DEV HM_NOINLINE void simt8_luma_winner_as_single_tu(Shared *e, TU tv);      // hm355_simt8.h
+template <int L2> HM_DEV HM_NOINLINE void simt_luma_winner_as_single_tu(Shared *e, TU tv);      // hm355_simt16.h
 HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirst)
 {
   HM_ENTRY(e); checkFirst = HM_UNI(checkFirst); rootv = hm_uni_struct(rootv);
@@ -2068,17 +2074,17 @@ HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirs
           f->singleDist = e->outDistY; f->singleBits = e->outBits;
           f->singleCost = calc_rd_cost(e, e->outBits, f->singleDist);
         } else if (sp == 0 && e->s8Reuse == 1) {
-          // closing pass of an 8x8 PU: its unsplit 8x8 TU is the evaluation the candidates-in-lanes first pass already made for the winner
+          // closing pass of an 8x8 / 16x16 PU: its unsplit TU is the evaluation the candidates-in-lanes first pass already made for the winner
           e->s8Reuse = 0;
           cabac_copy(&e->ws->slot[HM_SLOT(fullDepth, CI_QT_TRAFO_ROOT)], &e->cur);
           par_set8(m->ts[0] + z, 0, t->parts);
           par_set8(m->tr + z, t->trDepth, t->parts);
-          simt8_luma_winner_as_single_tu(e, *t);
+          if (log2 == 3) simt_luma_winner_as_single_tu<3>(e, *t); else simt_luma_winner_as_single_tu<4>(e, *t);
           f->singleDist = e->outDistY; f->singleCbf = e->outDist;
           par_set8(m->cbf[0] + z, (int)(f->singleCbf << t->trDepth), t->parts);
           f->singleCost = calc_rd_cost(e, e->outBits, f->singleDist);
         } else if (sp == 0 && e->s8Reuse == 2) {
-          // closing pass of a 16x16 / 32x32 PU: its unsplit TU is the winner's first-pass evaluation (same snapshot, same mode), whose levels and
+          // closing pass of a 32x32 PU: its unsplit TU is the winner's first-pass evaluation (same snapshot, same mode), whose levels and
           // reconstruction est_intra_pred_qt kept (xSetIntraResultQT) and whose estimator state it parked in this depth's CI_QT_TRAFO_TEST slot
           e->s8Reuse = 0;
           cabac_copy(&e->ws->slot[HM_SLOT(fullDepth, CI_QT_TRAFO_ROOT)], &e->cur);
@@ -2171,6 +2177,7 @@ HM_DEV inline void set_intra_result_qt(Shared *e, const TU *root)
 #include "hm355_simt.h"
 #include "hm355_simt4.h"
 #include "hm355_simt8.h"
+#include "hm355_simt16.h"
 
 // ------------------------------------------------------------------------------------------------
 // luma mode decision of one CU (TEncSearch::estIntraPredQT :2289-2692)
@@ -2257,15 +2264,14 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_qt(Shared *e, int cuZ, int cuDepth)
     }
     int bestPUMode = 0; uint32_t bestPUDistY = 0; double bestPUCost = HM_MAX_DOUBLE;
     int firstPass = 0;
-    if (n == 8) {
-      // 8x8 PU (2Nx2N CU of the smallest size): the first pass over the candidates only ranks them -- each is one unsplit 8x8 transform
-      // block from the same snapshot -- so it runs with the candidates in lanes (hm355_simt8.h) and only the closing pass with the full
-      // residual quadtree follows.  That pass starts with the very evaluation the winner had in the first pass, so its result is
+    if (n == 8 || n == 16) {
+      // 8x8 and 16x16 PUs (2Nx2N CUs of depth 3 and 2): the first pass over the candidates only ranks them -- each is one unsplit transform
+      // block from the same snapshot -- so it runs with the candidates in lanes (hm355_simt8.h, hm355_simt16.h) and only the closing pass with
+      // the full residual quadtree follows.  That pass starts with the very evaluation the winner had in the first pass, so its result is
       // the first-pass result or better, and is taken as the reference takes it (:2566-2600).
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
-      HM_PROF_BEGIN(e, PR_S8L);
-      bestPUMode = HM_UCALL(simt8_luma_first_pass(e, t, numModesForFullRD));
-      HM_PROF_END(e, PR_S8L);
+      if (n == 8) { HM_PROF_BEGIN(e, PR_S8L); bestPUMode = HM_UCALL(simt8_luma_first_pass(e, t, numModesForFullRD)); HM_PROF_END(e, PR_S8L); }
+      else { HM_PROF_BEGIN(e, PR_S16L); bestPUMode = HM_UCALL(simt16_luma_first_pass(e, t, numModesForFullRD)); HM_PROF_END(e, PR_S16L); }
       firstPass = numModesForFullRD;
       e->s8Reuse = 1;
     }
@@ -2274,9 +2280,9 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_qt(Shared *e, int cuZ, int cuDepth)
       const int orgMode = last ? bestPUMode : rdModeList[pass];
       par_set8(m->dirL + z, orgMode, puParts);
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
-      // 16x16 / 32x32 PUs: the closing pass takes its unsplit TU from the winner's first-pass evaluation instead of repeating it
+      // 32x32 PUs: the closing pass takes its unsplit TU from the winner's first-pass evaluation instead of repeating it
       e->outCost = bestPUCost;               // what this candidate has to beat (recur_intra_coding_qt gives up on a 64x64 PU that cannot)
-      if (last && (n == 16 || n == 32) && numModesForFullRD > 0) { e->s8Reuse = 2; e->outDistY = bestPUDistY; e->outRdCost = bestPUCost; }
+      if (last && n == 32 && numModesForFullRD > 0) { e->s8Reuse = 2; e->outDistY = bestPUDistY; e->outRdCost = bestPUCost; }
       recur_intra_coding_qt(e, t, !last);
       const uint32_t puDistY = e->outDistY; const double puCost = e->outRdCost;
       if (puCost < bestPUCost) {
@@ -2284,7 +2290,7 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_qt(Shared *e, int cuZ, int cuDepth)
         set_intra_result_qt(e, &t);
         HM_PAR_FOR(i, puParts) { ws->tmpTr[i] = m->tr[z + i]; for (int c = 0; c < 3; c++) { ws->tmpCbf[c][i] = m->cbf[c][z + i]; ws->tmpTs[c][i] = m->ts[c][z + i]; } }
         HM_SYNC();
-        if (!last && (n == 16 || n == 32)) cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_QT_TRAFO_TEST)], &e->cur);
+        if (!last && n == 32) cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_QT_TRAFO_TEST)], &e->cur);
       }
     }
     overallDistY += bestPUDistY;

@@ -1,12 +1,14 @@
-// hm355 -- candidates in lanes: what the 4x4 batches (hm355_simt4.h) and the 8x8 batches (hm355_simt8.h) share.
+// hm355 -- candidates in lanes: what the 4x4 batches (hm355_simt4.h), the 8x8 batches (hm355_simt8.h) and the 16x16 batches (hm355_simt16.h) share.
 //
-// One per-lane coefficient coder, parameterised by the block's log2 size L2 (2: one coefficient group, 3: four): the batch's
+// One per-lane coefficient coder, parameterised by the block's log2 size L2 (2: one coefficient group, 3: four, 4: sixteen): the batch's
 // tables (simt_setup), a context-coded bin on a job's private context copy (simt_bin), RDOQ (simt_rdoq =
 // TComTrQuant::xRateDistOptQuant) and the bit count of the coefficients (simt_code_coeff = TEncSbac::codeCoeffNxN), in the
 // reference's arithmetic and operation order -- the one-candidate-per-lane form of rdoq / code_coeff_nxn in hm355_core.h.
-// Simt<L2> (defined by the two headers) holds the LDS overlays of a batch and hides where each size keeps its data:
-//   A->tab, A->ctx, A->lps, B->dc, B->scan   the same members in both
-//   cs(sp, k)                                coefficient of job k at scan position sp
+// Simt<L2> (defined by the size's header) holds the LDS overlays of a batch and hides where each size keeps its data:
+//   tab(), ctx(c, k), lps()                  bit costs of the batch's start state, context copy c of job k, the LPS transitions
+//   cs(sp, k), scan_pos(scanType, sp)        coefficient of job k at scan position sp; raster position of a scan position
+//   put_dec / dec / mark_zeroed / zeroed     level of job k at decision time, and whether RDOQ zeroed its group afterwards
+//   put_lev / lev                            final signed level of job k
 //   cg_pos(scanType, cg)                     raster position of coefficient group cg
 //   sig_inc(scanType, firstCtx, pattern, sp, chroma)   significance context increment
 //   KEEPS_COST, keep_cost(), cost_at()       whether RDOQ stores the cost of each decided level (4x4) or prices it again (8x8)
@@ -16,15 +18,21 @@
 // Context numbering inside a batch: X_* index the per-job context copies (Simt<L2>::A->ctx), T_* the bit costs of the batch's
 // start state (A->tab, two entries per context: bin 0, bin 1).  Significance contexts by their increment, greater-than-1 contexts
 // 4 * set + c1 with set = 0..3 for luma and 0..1 for chroma (whose sets are 4, 5 in the reference's numbering), greater-than-2 by
-// set, the three last-position contexts a block of this size uses per coordinate, the two coded-sub-block contexts (8x8), cbf,
+// set, the NLAST last-position contexts a block of this size uses per coordinate, the two coded-sub-block contexts (8x8), cbf,
 // the prediction-mode bin, the transform-skip flag (4x4).  T_LASTX / T_LASTY hold the cost of each last-position group index.
 template <int L2> struct SimtDim {
-  enum { NC = 1 << (2 * L2), NCG = NC / 16, NSIG = L2 == 2 ? 9 : 21, NSET = NCG == 1 ? 1 : 4, NGRP = 2 * L2, NCGC = NCG == 1 ? 0 : 2,
-         X_SIG = 0, X_ONE = NSIG, X_ABS = X_ONE + 4 * NSET, X_LX = X_ABS + NSET, X_LY = X_LX + 3, X_CG = X_LY + 3, X_CBF = X_CG + NCGC,
+  enum { NC = 1 << (2 * L2), NCG = NC / 16, WCG = 1 << (L2 - 2), NSIG = L2 == 2 ? 9 : (L2 == 3 ? 21 : 27), NSET = NCG == 1 ? 1 : 4, NGRP = 2 * L2, NCGC = NCG == 1 ? 0 : 2,
+         NLAST = L2 == 4 ? 4 : 3, LSH = L2 == 4 ? 1 : L2 - 2,   // last-position contexts per coordinate; group index -> context shift (a 16x16 block is luma only)
+         X_SIG = 0, X_ONE = NSIG, X_ABS = X_ONE + 4 * NSET, X_LX = X_ABS + NSET, X_LY = X_LX + NLAST, X_CG = X_LY + NLAST, X_CBF = X_CG + NCGC,
          X_MODE = X_CBF + 1, X_TSKIP = X_MODE + 1, NCTX = X_TSKIP + (L2 == 2 ? 1 : 0),
          T_SIG = 0, T_ONE = 2 * NSIG, T_ABS = T_ONE + 8 * NSET, T_LASTX = T_ABS + 2 * NSET, T_LASTY = T_LASTX + NGRP, T_CG = T_LASTY + NGRP,
          T_CBF = T_CG + 2 * NCGC, T_N = T_CBF + 2 };
 };
+static_assert(SimtDim<2>::NCTX == 23 && SimtDim<2>::T_N == 38 && SimtDim<2>::X_LX == 14 && SimtDim<2>::X_LY == 17 && SimtDim<2>::X_CBF == 20 && SimtDim<2>::T_LASTX == 28 &&
+              SimtDim<2>::T_LASTY == 32 && SimtDim<2>::T_CBF == 36 && SimtDim<2>::LSH == 0, "the 4x4 batch's numbering");
+static_assert(SimtDim<3>::NCTX == 51 && SimtDim<3>::T_N == 100 && SimtDim<3>::X_ONE == 21 && SimtDim<3>::X_ABS == 37 && SimtDim<3>::X_LX == 41 && SimtDim<3>::X_LY == 44 &&
+              SimtDim<3>::X_CG == 47 && SimtDim<3>::X_CBF == 49 && SimtDim<3>::T_ONE == 42 && SimtDim<3>::T_ABS == 74 && SimtDim<3>::T_LASTX == 82 && SimtDim<3>::T_LASTY == 88 &&
+              SimtDim<3>::T_CG == 94 && SimtDim<3>::T_CBF == 98 && SimtDim<3>::LSH == 1 && SimtDim<3>::WCG == 2, "the 8x8 batch's numbering");
 template <int L2> struct Simt;
 template <int L2> struct SimtPrices {     // greater-than-1 / greater-than-2 prices of ic_rate in the batch's table
   const int32_t *tab;
@@ -67,7 +75,7 @@ HM_FINL int simt_dequant(const SimtPar &p, int level)
 template <int L2> HM_FINL int simt_ctx_index(int j, int chroma, int cbfCodeCtx, int modeCtx)
 {
   typedef SimtDim<L2> D;
-  const int lastOff = chroma ? 15 : (L2 == 2 ? 0 : 3);              // getLastSignificantContextParameters (last_ctx_params)
+  const int lastOff = chroma ? 15 : 3 * (L2 - 2);              // getLastSignificantContextParameters (last_ctx_params)
   if (j < D::X_ONE) return C_SIG + (chroma ? 28 : 0) + (chroma && j >= 16 ? 0 : j);
   if (j < D::X_ABS) return C_ONE + (chroma ? 16 + ((j - D::X_ONE) & 7) : j - D::X_ONE);
   if (j < D::X_LX) return C_ABS + (chroma ? 4 + ((j - D::X_ABS) & 1) : j - D::X_ABS);
@@ -90,19 +98,19 @@ template <int L2> HM_DEV inline void simt_setup(Shared *e, const Simt<L2> &S, co
     if (i < D::T_LASTX) {                 // the contexts in front of the last-position ones: same order in the table and in the copies
       const int j = i >> 1, none = chroma && ((j < D::X_ONE && j >= 16) || (j >= D::X_ONE && j < D::X_ABS && j - D::X_ONE >= 8) || (j >= D::X_ABS && j - D::X_ABS >= 2));
       if (!none) v = HM_LT()->ebits[cb->s[simt_ctx_index<L2>(j, chroma, 0, 0)] ^ bin];
-    } else if (i < D::T_CG) { // last-position group index g: g ones on the contexts (c >> (L2 - 2)) of the block's three, then a zero unless g is the maximum; g > 3 adds bypass bits (xGetRateLast :2815)
+    } else if (i < D::T_CG) { // last-position group index g: g ones on the contexts (c >> LSH) of the block's NLAST, then a zero unless g is the maximum; g > 3 adds bypass bits (xGetRateLast :2815)
       const int g = (i - D::T_LASTX) % D::NGRP, x0 = i < D::T_LASTY ? D::X_LX : D::X_LY;
-      for (int c = 0; c < g; c++) v += HM_LT()->ebits[cb->s[simt_ctx_index<L2>(x0 + (c >> (L2 - 2)), chroma, 0, 0)] ^ 1];
-      if (g < D::NGRP - 1) v += HM_LT()->ebits[cb->s[simt_ctx_index<L2>(x0 + (g >> (L2 - 2)), chroma, 0, 0)] ^ 0];
+      for (int c = 0; c < g; c++) v += HM_LT()->ebits[cb->s[simt_ctx_index<L2>(x0 + (c >> D::LSH), chroma, 0, 0)] ^ 1];
+      if (g < D::NGRP - 1) v += HM_LT()->ebits[cb->s[simt_ctx_index<L2>(x0 + (g >> D::LSH), chroma, 0, 0)] ^ 0];
       if (g > 3) v += 32768 * ((g - 2) >> 1);
     } else if (i < D::T_CBF) v = HM_LT()->ebits[cb->s[simt_ctx_index<L2>(D::X_CG + ((i - D::T_CG) >> 1), chroma, 0, 0)] ^ bin];
     else v = HM_LT()->ebits[cb->s[C_QT_CBF + cbfCtx] ^ bin];
-    S.A->tab[i] = v;
+    S.tab()[i] = v;
   }
-  HM_PAR_FOR(i, 128) S.A->lps[i] = HM_NEXT_LPS[i];
+  HM_PAR_FOR(i, 128) S.lps()[i] = HM_NEXT_LPS[i];
   HM_PAR_FOR(i, D::NCTX * S.JOBS) {
     const int j = i / S.JOBS, k = i - j * S.JOBS;
-    if (k < jobs) S.A->ctx[j][k] = cb->s[simt_ctx_index<L2>(j, chroma, cbfCodeCtx, modeCtx)];
+    if (k < jobs) S.ctx(j, k) = cb->s[simt_ctx_index<L2>(j, chroma, cbfCodeCtx, modeCtx)];
   }
   S.load_scans(e);
   HM_SYNC();
@@ -110,21 +118,21 @@ template <int L2> HM_DEV inline void simt_setup(Shared *e, const Simt<L2> &S, co
 // the estimator after job k of a luma batch: the contexts the lane advanced
 template <int L2> HM_FINL void simt_store_contexts(const Simt<L2> &S, int k, Cabac *cb, int cbfCodeCtx)
 {
-  HM_PAR_FOR(j, SimtDim<L2>::NCTX) cb->s[simt_ctx_index<L2>(j, 0, cbfCodeCtx, C_INTRA_LUMA)] = S.A->ctx[j][k];
+  HM_PAR_FOR(j, SimtDim<L2>::NCTX) cb->s[simt_ctx_index<L2>(j, 0, cbfCodeCtx, C_INTRA_LUMA)] = S.ctx(j, k);
 }
 
 // one context-coded bin on job k's private context copy; frac counts Q15 bits
 template <int L2> HM_DEV inline void simt_bin(const Shared *e, const Simt<L2> &S, int k, uint32_t *frac, int c, int bin)
 {
-  const int st = S.A->ctx[c][k];
+  const int st = S.ctx(c, k);
   *frac += (uint32_t)HM_LT()->ebits[st ^ bin];
-  S.A->ctx[c][k] = (uint8_t)(bin == (st & 1) ? (st < 124 ? st + 2 : st) : S.A->lps[st]);
+  S.ctx(c, k) = (uint8_t)(bin == (st & 1) ? (st < 124 ? st + 2 : st) : S.lps()[st]);
 }
-// calcPatternSigCtx / getSigCoeffGroupCtxInc: the coded flags of the groups right of and below the one at cgBlkPos (two groups per row)
-HM_FINL int simt_cg_pattern(int cgBlkPos, int cgMask)
+// calcPatternSigCtx / getSigCoeffGroupCtxInc: the coded flags of the groups right of and below the one at cgBlkPos (WCG groups per row)
+template <int L2> HM_FINL int simt_cg_pattern(int cgBlkPos, int cgMask)
 {
-  const int cgx = cgBlkPos & 1, cgy = cgBlkPos >> 1;
-  const int sigRight = cgx < 1 ? ((cgMask >> (cgBlkPos + 1)) & 1) : 0, sigLower = cgy < 1 ? ((cgMask >> (cgBlkPos + 2)) & 1) : 0;
+  const int W = SimtDim<L2>::WCG, cgx = cgBlkPos & (W - 1), cgy = cgBlkPos >> (L2 - 2);
+  const int sigRight = cgx < W - 1 ? ((cgMask >> (cgBlkPos + 1)) & 1) : 0, sigLower = cgy < W - 1 ? ((cgMask >> (cgBlkPos + W)) & 1) : 0;
   return sigRight + (sigLower << 1);
 }
 // raster position -> (x, y) of the last-position syntax (swapped for the vertical scan)
@@ -135,30 +143,29 @@ template <int L2> HM_FINL void simt_last_xy(int blkPos, int scanType, int *px, i
 }
 
 // RDOQ of job k's block (TComTrQuant::xRateDistOptQuant, TComTrQuant.cpp:1974-2511): coefficients in S.cs(., k) (scan order); leaves the
-// signed levels in the high halves of B->dc[.][k] (level at decision time in the low half) and returns the sum of their magnitudes.
+// signed levels in S.lev(., k) (level at decision time in S.dec(., k)) and returns the sum of their magnitudes.
 template <int L2> HM_DEV inline int simt_rdoq(const Simt<L2> &S, const SimtPar &p, int k, int scanType)
 {
   typedef SimtDim<L2> D;
-  const int32_t *tab = S.A->tab; const SimtPrices<L2> prices = { tab };
+  const int32_t *tab = S.tab(); const SimtPrices<L2> prices = { tab };
   const int qBits = p.qBits, half = 1 << (qBits - 1);
   const double lambda = p.lambda, errScale = p.errScale;
   const int firstCtx = first_sig_ctx(1 << L2, scanType, p.chroma), lumaSets = p.chroma ? 0 : 2;      // luma: coefficient groups behind the first use context sets 2, 3
   double blockUncoded = 0, baseCost = 0;
-  double cgSig1 = 0, cgSig2 = 0, cgSig3 = 0;                      // cost of the coded-sub-block flag per group (scan order)
   int last = -1, cgLast = -1, ctxSet = 0;
-  int cgMask = 0, cgSets = 0;                                     // group flags (bit = raster position of the group); context set each group started with
+  int cgMask = 0; uint32_t cgSets = 0;                            // group flags (bit = raster position of the group); context set each group started with (two bits per group)
   LevelChain ch;
   for (int cg = D::NCG - 1; cg >= 0; cg--) {
-    const int cgBlkPos = S.cg_pos(scanType, cg), cgBit = 1 << cgBlkPos, pattern = simt_cg_pattern(cgBlkPos, cgMask);
+    const int cgBlkPos = S.cg_pos(scanType, cg), cgBit = 1 << cgBlkPos, pattern = simt_cg_pattern<L2>(cgBlkPos, cgMask);
     double sigCost = 0, sigCost0 = 0, codedLevelAndDist = 0, uncodedDist = 0; int nnzBeforePos0 = 0;
-    cgSets |= ctxSet << (2 * cg);
+    cgSets |= (uint32_t)ctxSet << (2 * cg);
     for (int q = 15; q >= 0; q--) {
       const int sp = cg * 16 + q;
       const int32_t lvlD = simt_level_double(S.cs(sp, k), p);
       uint32_t mx = (uint32_t)((lvlD + half) >> qBits); if (mx > 32767u) mx = 32767u;
       const double err = (double)lvlD, c0 = err * err * errScale;
       blockUncoded += c0;
-      if (mx > 0 && last < 0) { last = sp; cgLast = cg; ctxSet = cg > 0 ? lumaSets : 0; cgSets = ctxSet << (2 * cg); }
+      if (mx > 0 && last < 0) { last = sp; cgLast = cg; ctxSet = cg > 0 ? lumaSets : 0; cgSets = (uint32_t)ctxSet << (2 * cg); }
       uint32_t level = 0; double cSig = 0, cCoeff = c0;
       if (last >= 0) {
         const int isLast = (sp == last);
@@ -191,30 +198,26 @@ template <int L2> HM_DEV inline int simt_rdoq(const Simt<L2> &S, const SimtPar &
         uncodedDist += c0;
         if (q != 0) nnzBeforePos0++;
       }
-      S.B->dc[sp][k] = (int32_t)level;
+      S.put_dec(sp, k, level);
     }
     if (cgLast >= 0) {
       if (cg) {
         const int cgCtx = (pattern != 0) * 2;                                              // getSigCoeffGroupCtxInc :2872
-        double cgs = 0;
         if (!(cgMask & cgBit)) {
           const double r0 = lambda * (double)tab[D::T_CG + cgCtx];
           baseCost += r0 - sigCost;
-          cgs = r0;
         } else if (cg < cgLast) {
           if (nnzBeforePos0 == 0) { baseCost -= sigCost0; sigCost -= sigCost0; }
           double costZeroCG = baseCost;
           const double r0 = lambda * (double)tab[D::T_CG + cgCtx], r1 = lambda * (double)tab[D::T_CG + cgCtx + 1];
           baseCost += r1;
           costZeroCG += r0;
-          cgs = r1;
           costZeroCG += uncodedDist; costZeroCG -= codedLevelAndDist; costZeroCG -= sigCost;
           if (costZeroCG < baseCost) {
-            cgMask &= ~cgBit; baseCost = costZeroCG; cgs = r0;
-            for (int q = 15; q >= 0; q--) S.B->dc[cg * 16 + q][k] |= 0x40000000;      // zeroed: the decision-time level stays for the walks below
+            cgMask &= ~cgBit; baseCost = costZeroCG;
+            for (int q = 15; q >= 0; q--) S.mark_zeroed(cg * 16 + q, k);          // the decision-time level stays for the walks below
           }
         }
-        if (cg == 1) cgSig1 = cgs; else if (cg == 2) cgSig2 = cgs; else cgSig3 = cgs;
       } else cgMask |= cgBit;
     }
   }
@@ -223,15 +226,20 @@ template <int L2> HM_DEV inline int simt_rdoq(const Simt<L2> &S, const SimtPar &
   baseCost += lambda * (double)tab[D::T_CBF + 1];
   int bestLastP1 = 0, found = 0;
   for (int cg = cgLast; cg >= 0 && !found; cg--) {
-    if (cg) baseCost -= (cg == 1 ? cgSig1 : (cg == 2 ? cgSig2 : cgSig3));
-    if (!((cgMask >> S.cg_pos(scanType, cg)) & 1)) continue;
+    // the cost the decision loop added for the group's coded-sub-block flag, priced again: none for the last group, else the flag the group
+    // ended up with on the context its right and lower neighbours gave it (both were settled before the group itself was decided).  The
+    // group of the last position adds none because it always stays coded: the level decided at the last position is at least 1 (its zero
+    // hypothesis costs HM_MAX_DOUBLE), so that group never takes the uncoded branch that would have added the price of a 0 flag.
+    const int cgBlkPos = S.cg_pos(scanType, cg), coded = (cgMask >> cgBlkPos) & 1, pattern = simt_cg_pattern<L2>(cgBlkPos, cgMask);
+    if (cg && cg < cgLast) baseCost -= lambda * (double)tab[D::T_CG + (pattern != 0) * 2 + coded];
+    if (!coded) continue;
     // the decision chain's state inside this group, walked again where the levels it decided are priced again
-    const int wSet = (cgSets >> (2 * cg)) & 3, pattern = simt_cg_pattern(S.cg_pos(scanType, cg), cgMask); LevelChain walk;
+    const int wSet = (int)((cgSets >> (2 * cg)) & 3); LevelChain walk;
     for (int q = (cg == cgLast ? (last & 15) : 15); q >= 0; q--) {
-      const int sp = cg * 16 + q, lev = S.B->dc[sp][k] & 0xffff;
+      const int sp = cg * 16 + q, lev = S.dec(sp, k);
       const int si = sp == last ? 0 : S.sig_inc(scanType, firstCtx, pattern, sp, p.chroma);
       if (lev) {
-        int px, py; simt_last_xy<L2>(S.B->scan[scanType][sp], scanType, &px, &py);
+        int px, py; simt_last_xy<L2>(S.scan_pos(scanType, sp), scanType, &px, &py);
         const double costLast = lambda * (double)(tab[D::T_LASTX + hm_group_idx(px)] + tab[D::T_LASTY + hm_group_idx(py)]);
         const double cSig = (sp == last) ? 0.0 : lambda * (double)tab[D::T_SIG + si * 2 + 1];
         const double t1 = baseCost + costLast;
@@ -257,9 +265,9 @@ template <int L2> HM_DEV inline int simt_rdoq(const Simt<L2> &S, const SimtPar &
   // levels with signs: zeroed groups and everything behind the chosen last position become 0
   int absSum = 0;
   for (int sp = 0; sp < D::NC; sp++) {
-    const int v = S.B->dc[sp][k], dec = v & 0xffff, lv = (sp < bestLastP1 && !(v & 0x40000000)) ? dec : 0;
+    const int lv = (sp < bestLastP1 && !S.zeroed(sp, k)) ? S.dec(sp, k) : 0;
     absSum += lv;
-    S.B->dc[sp][k] = dec | (int32_t)((uint32_t)(S.cs(sp, k) < 0 ? -lv : lv) << 16);
+    S.put_lev(sp, k, S.cs(sp, k) < 0 ? -lv : lv);
   }
   // sign bit hiding, TComTrQuant.cpp:2380-2510
   if (absSum >= 2) {
@@ -267,18 +275,18 @@ template <int L2> HM_DEV inline int simt_rdoq(const Simt<L2> &S, const SimtPar &
     for (int subSet = D::NCG - 1; subSet >= 0; subSet--) {
       const int subPos = subSet << 4;
       int lastNZ = -1, firstNZ = 16, parity = 0;
-      for (int q = 0; q < 16; q++) { const int lv = S.B->dc[subPos + q][k] >> 16; if (lv) { lastNZ = q; if (firstNZ == 16) firstNZ = q; } parity ^= lv & 1; }
+      for (int q = 0; q < 16; q++) { const int lv = S.lev(subPos + q, k); if (lv) { lastNZ = q; if (firstNZ == 16) firstNZ = q; } parity ^= lv & 1; }
       if (lastNZ >= 0 && lastCG == -1) lastCG = 1;
       if (lastNZ - firstNZ >= 4) {
-        const uint32_t signbit = (S.B->dc[subPos + firstNZ][k] >> 16) > 0 ? 0 : 1;
+        const uint32_t signbit = S.lev(subPos + firstNZ, k) > 0 ? 0 : 1;
         if (signbit != (uint32_t)parity) {
           const int64_t I64MAX = 0x7fffffffffffffffLL;
           int64_t minCostInc = I64MAX, curCost = I64MAX; int minK = -1, finalChange = 0, curChange = 0;
-          const int wSet = (cgSets >> (2 * subSet)) & 3; LevelChain walk;          // the decision chain's state, walked again
+          const int wSet = (int)((cgSets >> (2 * subSet)) & 3); LevelChain walk;   // the decision chain's state, walked again
           const int top = (subPos + 15 <= last) ? 15 : (last - subPos), kStart = (lastCG == 1 ? lastNZ : 15);
-          const int pattern = simt_cg_pattern(S.cg_pos(scanType, subSet), cgMask);
+          const int pattern = simt_cg_pattern<L2>(S.cg_pos(scanType, subSet), cgMask);
           for (int q = top; q >= 0; --q) {
-            const int v = S.B->dc[subPos + q][k]; const uint32_t dec = (uint32_t)(v & 0xffff); const int dv = v >> 16;
+            const uint32_t dec = (uint32_t)S.dec(subPos + q, k); const int dv = S.lev(subPos + q, k);
             const int ctxOne = 4 * wSet + walk.c1; const LevelChain at = walk;
             walk.step(dec);
             if (q > kStart) continue;
@@ -307,10 +315,10 @@ template <int L2> HM_DEV inline int simt_rdoq(const Simt<L2> &S, const SimtPar &
             if (curCost < minCostInc) { minCostInc = curCost; finalChange = curChange; minK = q; }
           }
           if (minK >= 0) {
-            const int v = S.B->dc[subPos + minK][k]; int mv = v >> 16;
+            int mv = S.lev(subPos + minK, k);
             if (mv == 32767 || mv == -32768) finalChange = -1;
             mv = (S.cs(subPos + minK, k) < 0) ? mv - finalChange : mv + finalChange;
-            S.B->dc[subPos + minK][k] = (v & 0xffff) | (int32_t)((uint32_t)mv << 16);
+            S.put_lev(subPos + minK, k, mv);
           }
         }
       }
@@ -320,22 +328,22 @@ template <int L2> HM_DEV inline int simt_rdoq(const Simt<L2> &S, const SimtPar &
   return absSum;
 }
 
-// TEncSbac::codeCoeffNxN, TEncSbac.cpp:1172-1525, of a block on job k's private contexts (bits only): the levels are the high halves of
-// B->dc[.][src] (job `src` evaluated the block; k codes it).  The transform-skip flag of a 4x4 block is the caller's.
+// TEncSbac::codeCoeffNxN, TEncSbac.cpp:1172-1525, of a block on job k's private contexts (bits only): the levels are
+// S.lev(., src) (job `src` evaluated the block; k codes it).  The transform-skip flag of a 4x4 block is the caller's.
 template <int L2> HM_DEV inline void simt_code_coeff(const Shared *e, const Simt<L2> &S, int k, int src, int chroma, int scanType, uint32_t *frac)
 {
   typedef SimtDim<L2> D;
   int last = -1, cgMask = 0;
   for (int sp = 0; sp < D::NC; sp++)
-    if ((S.B->dc[sp][src] >> 16) != 0) { last = sp; cgMask |= 1 << S.cg_pos(scanType, sp >> 4); }
+    if (S.lev(sp, src) != 0) { last = sp; cgMask |= 1 << S.cg_pos(scanType, sp >> 4); }
   { // codeLastSignificantXY :1106: the group index of each coordinate on the block's three contexts, then its bypass suffix
-    int px, py; simt_last_xy<L2>(S.B->scan[scanType][last], scanType, &px, &py);
+    int px, py; simt_last_xy<L2>(S.scan_pos(scanType, last), scanType, &px, &py);
     const int gx = hm_group_idx(px), gy = hm_group_idx(py);
     int q;
-    for (q = 0; q < gx; q++) simt_bin(e, S, k, frac, D::X_LX + (q >> (L2 - 2)), 1);
-    if (gx < D::NGRP - 1) simt_bin(e, S, k, frac, D::X_LX + (q >> (L2 - 2)), 0);
-    for (q = 0; q < gy; q++) simt_bin(e, S, k, frac, D::X_LY + (q >> (L2 - 2)), 1);
-    if (gy < D::NGRP - 1) simt_bin(e, S, k, frac, D::X_LY + (q >> (L2 - 2)), 0);
+    for (q = 0; q < gx; q++) simt_bin(e, S, k, frac, D::X_LX + (q >> D::LSH), 1);
+    if (gx < D::NGRP - 1) simt_bin(e, S, k, frac, D::X_LX + (q >> D::LSH), 0);
+    for (q = 0; q < gy; q++) simt_bin(e, S, k, frac, D::X_LY + (q >> D::LSH), 1);
+    if (gy < D::NGRP - 1) simt_bin(e, S, k, frac, D::X_LY + (q >> D::LSH), 0);
     if (gx > 3) *frac += 32768u * (uint32_t)((gx - 2) >> 1);
     if (gy > 3) *frac += 32768u * (uint32_t)((gy - 2) >> 1);
   }
@@ -343,14 +351,14 @@ template <int L2> HM_DEV inline void simt_code_coeff(const Shared *e, const Simt
   int c1 = 1;
   for (int subSet = lastSet; subSet >= 0; subSet--) {
     const int subPos = subSet << 4, isLastSet = subSet == lastSet;
-    const int cgBlkPos = S.cg_pos(scanType, subSet), pattern = simt_cg_pattern(cgBlkPos, cgMask);
+    const int cgBlkPos = S.cg_pos(scanType, subSet), pattern = simt_cg_pattern<L2>(cgBlkPos, cgMask);
     if (isLastSet || subSet == 0) cgMask |= 1 << cgBlkPos;            // coded-sub-block flag: implied for the last group and the first
     else simt_bin(e, S, k, frac, D::X_CG + (pattern != 0), (cgMask >> cgBlkPos) & 1);
     if (!((cgMask >> cgBlkPos) & 1)) continue;
     const int top = isLastSet ? (last & 15) : 15;
     int numNonZero = isLastSet ? 1 : 0, firstNZ = isLastSet ? top : 16, lastNZ = isLastSet ? top : -1;
     for (int q = isLastSet ? top - 1 : 15; q >= 0; q--) {           // significance flags; the last coefficient itself is implied
-      const int sig = (S.B->dc[subPos + q][src] >> 16) != 0;
+      const int sig = S.lev(subPos + q, src) != 0;
       if (q > 0 || subSet == 0 || numNonZero) simt_bin(e, S, k, frac, D::X_SIG + S.sig_inc(scanType, firstCtx, pattern, subPos + q, chroma), sig);
       if (sig) { numNonZero++; firstNZ = q; if (lastNZ < 0) lastNZ = q; }
     }
@@ -360,7 +368,7 @@ template <int L2> HM_DEV inline void simt_code_coeff(const Shared *e, const Simt
       c1 = 1;
       int firstC2 = -1, escape = 0, idx = 0;
       for (int q = lastNZ; q >= 0 && idx < 8; q--) {
-        const int a = hm_abs(S.B->dc[subPos + q][src] >> 16);
+        const int a = hm_abs(S.lev(subPos + q, src));
         if (!a) continue;
         const int sym = a > 1;
         simt_bin(e, S, k, frac, D::X_ONE + 4 * ctxSet + c1, sym);
@@ -368,13 +376,13 @@ template <int L2> HM_DEV inline void simt_code_coeff(const Shared *e, const Simt
         else if (c1 < 3 && c1 > 0) c1++;
         idx++;
       }
-      if (c1 == 0 && firstC2 != -1) { const int sym = hm_abs(S.B->dc[subPos + firstC2][src] >> 16) > 2; simt_bin(e, S, k, frac, D::X_ABS + ctxSet, sym); if (sym) escape = 1; }
+      if (c1 == 0 && firstC2 != -1) { const int sym = hm_abs(S.lev(subPos + firstC2, src)) > 2; simt_bin(e, S, k, frac, D::X_ABS + ctxSet, sym); if (sym) escape = 1; }
       escape = escape || (numNonZero > 8);
       *frac += 32768u * (uint32_t)(signHidden ? numNonZero - 1 : numNonZero);
       if (escape) {
         int firstCoeff2 = 1; uint32_t goRice = 0; idx = 0;
         for (int q = lastNZ; q >= 0; q--) {
-          const int a = hm_abs(S.B->dc[subPos + q][src] >> 16);
+          const int a = hm_abs(S.lev(subPos + q, src));
           if (!a) continue;
           const int baseLevel = (idx < 8) ? (2 + firstCoeff2) : 1;
           if (a >= baseLevel) {

@@ -50,6 +50,17 @@ template <> struct Simt<2> {              // a batch of 4x4 blocks: RDOQ keeps t
   enum { JOBS = HM_SL, KEEPS_COST = 1 };
   Simt4A *A; Simt4B *B;
   HM_FINL_M explicit Simt(Shared *e) : A((Simt4A *)e->bufA), B((Simt4B *)((char *)&e->u + offsetof(RefLds, refMain))) {}
+  HM_FINL_M int32_t *tab() const { return A->tab; }
+  HM_FINL_M uint8_t &ctx(int c, int k) const { return A->ctx[c][k]; }
+  HM_FINL_M uint8_t *lps() const { return A->lps; }
+  HM_FINL_M int scan_pos(int scanType, int sp) const { return B->scan[scanType][sp]; }
+  // B->dc: level at decision time in the low half, the final signed level in the high half, bit 30 marks a group RDOQ zeroed
+  HM_FINL_M void put_dec(int sp, int k, uint32_t level) const { B->dc[sp][k] = (int32_t)level; }
+  HM_FINL_M void mark_zeroed(int sp, int k) const { B->dc[sp][k] |= 0x40000000; }
+  HM_FINL_M int dec(int sp, int k) const { return B->dc[sp][k] & 0xffff; }
+  HM_FINL_M int zeroed(int sp, int k) const { return B->dc[sp][k] & 0x40000000; }
+  HM_FINL_M void put_lev(int sp, int k, int v) const { B->dc[sp][k] = (B->dc[sp][k] & 0xffff) | (int32_t)((uint32_t)v << 16); }
+  HM_FINL_M int lev(int sp, int k) const { return B->dc[sp][k] >> 16; }
   HM_FINL_M int cs(int sp, int k) const { return B->cs[sp][k]; }
   HM_FINL_M int cg_pos(int, int) const { return 0; }
   HM_FINL_M int sig_inc(int scanType, int, int, int sp, int) const { return B->sigIdx[scanType][sp]; }

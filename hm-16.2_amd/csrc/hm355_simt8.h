@@ -31,6 +31,17 @@ template <> struct Simt<3> {              // a batch of 8x8 blocks: RDOQ prices 
   enum { JOBS = HM_S8, KEEPS_COST = 0 };
   Simt8A *A; Simt8B *B;
   HM_FINL_M explicit Simt(Shared *e) : A((Simt8A *)e->bufA), B((Simt8B *)((char *)&e->u + offsetof(RefLds, refMain))) {}
+  HM_FINL_M int32_t *tab() const { return A->tab; }
+  HM_FINL_M uint8_t &ctx(int c, int k) const { return A->ctx[c][k]; }
+  HM_FINL_M uint8_t *lps() const { return A->lps; }
+  HM_FINL_M int scan_pos(int scanType, int sp) const { return B->scan[scanType][sp]; }
+  // B->dc: level at decision time in the low half, the final signed level in the high half, bit 30 marks a group RDOQ zeroed
+  HM_FINL_M void put_dec(int sp, int k, uint32_t level) const { B->dc[sp][k] = (int32_t)level; }
+  HM_FINL_M void mark_zeroed(int sp, int k) const { B->dc[sp][k] |= 0x40000000; }
+  HM_FINL_M int dec(int sp, int k) const { return B->dc[sp][k] & 0xffff; }
+  HM_FINL_M int zeroed(int sp, int k) const { return B->dc[sp][k] & 0x40000000; }
+  HM_FINL_M void put_lev(int sp, int k, int v) const { B->dc[sp][k] = (B->dc[sp][k] & 0xffff) | (int32_t)((uint32_t)v << 16); }
+  HM_FINL_M int lev(int sp, int k) const { return B->dc[sp][k] >> 16; }
   HM_FINL_M int cs(int sp, int k) const { return A->cs[sp][k]; }
   HM_FINL_M int cg_pos(int scanType, int cg) const { return B->scanCG[scanType][cg]; }
   HM_FINL_M int sig_inc(int scanType, int firstCtx, int pattern, int sp, int chroma) const { return sig_ctx_inc(pattern, firstCtx, B->scan[scanType][sp], 3, chroma); }
@@ -162,7 +173,7 @@ HM_DEV HM_NOINLINE int simt8_luma_first_pass(Shared *e, TU tv, int numModes)
   for (int c = 0; c < numModes; c++) { const double v = A->outCost[c]; if (v < bestCost) { bestCost = v; best = c; } }
   best = HM_UNI(best);
   const int bestMode = e->rdModeList[best];
-  e->s8Winner = best;                                              // simt8_luma_winner_as_single_tu picks the winner's evaluation up from the overlays
+  e->s8Winner = best | (best << 8);                                // slot and place in the list: simt_luma_winner_as_single_tu (hm355_simt16.h) picks the winner's evaluation up from the overlays
   HM_SYNC();
   return bestMode;
 }
@@ -253,39 +264,4 @@ HM_DEV HM_NOINLINE uint32_t simt8_chroma_cu16(Shared *e, int cuZ)
   HM_PAR_FOR(i, 16) { m->cbf[1][cuZ + i] = (uint8_t)cbfU; m->cbf[2][cuZ + i] = (uint8_t)cbfV; m->ts[1][cuZ + i] = 0; m->ts[2][cuZ + i] = 0; m->dirC[cuZ + i] = (uint8_t)bm; }
   HM_SYNC();
   return bestDist;
-}
-
-// The closing pass of estIntraPredQT (:2566-2600) starts with the unsplit evaluation of the winner's 8x8 transform block -- the very
-// evaluation the first pass above made for it, from the same snapshot.  Instead of repeating it (xIntraCodingTUBlock + xGetIntraBitsQT), the
-// winner's results are put where the residual quadtree expects them: levels and reconstruction in the layer buffers of the 8x8 size, the
-// estimator (e->cur) advanced past the block's syntax (the bins every candidate codes alike, then the contexts and the bit count of the
-// winner's lane).  Must run right after simt8_luma_first_pass (the overlays and the reference lines are still in place), with e->cur
-// holding the CU's entry snapshot.  Distortion / bits / cbf in e->outDistY / e->outBits / e->outDist.
-HM_DEV HM_NOINLINE void simt8_luma_winner_as_single_tu(Shared *e, TU tv)
-{
-  HM_ENTRY(e); tv = hm_uni_struct(tv);
-  const TU *t = &tv; WorkSpace *ws = e->ws;
-  const Simt8 S(e); Simt8A *A = S.A;
-  const int best = HM_UNI(e->s8Winner), z = t->cuZ + t->relZ, ps = e->stride[0], bitDepth = e->bitDepth;
-  const int mode = e->rdModeList[best], cbf = A->outCbf[best];
-  const SimtPar p = simt_params<3>(e, 0);
-  const int dcVal = ref_dc_val(e, 0, 8);
-  Pel *rq = ws->qtRec[2] + t->y * 64 + t->x;
-  Pel *recPic = e->fb.rec[0] + (e->ctuY * 64 + t->y) * ps + e->ctuX * 64 + t->x;
-  s8_dequant_inv1(S, p, intra_scan_type(mode), best, cbf, ws->qtCoef[2] + z * 16);
-  s8_inv2_recon(S, bitDepth, cbf, [&](int x, int y) HM_LAMBDA_INL { return pred_sample(e, mode, 8, 3, x, y, dcVal, bitDepth); },
-                [&](int x, int y, int rr) HM_LAMBDA_INL { rq[y * 64 + x] = (Pel)rr; recPic[y * ps + x] = (Pel)rr; });
-  HM_SYNC();
-  { // the estimator: the bins in front of the lane's own (same as simt8_luma_first_pass counted), then the lane's contexts and bit count
-    CabacR r; cabr_load(e, r, &e->cur);
-    r.frac &= 32767;
-    if (e->im) { code_skip_flag(e, &r, t->cuZ); enc_bin(e, &r, C_PRED_MODE, 1); }
-    enc_bin(e, &r, C_PART, 1);
-    enc_bin(e, &r, C_SUBDIV + 2, 0);
-    cabr_store(r, &e->cur);
-  }
-  simt_store_contexts(S, best, &e->cur, 1);
-  e->cur.frac = (uint64_t)A->outFrac[best];
-  e->outDistY = A->outDist[best]; e->outBits = A->outFrac[best] >> 15; e->outDist = (uint32_t)cbf;
-  HM_SYNC();
 }

@@ -1,0 +1,46 @@
+"""GPU suite (-m gpu): the candidates-in-lanes first pass of 16x16 intra PUs (hm355_simt16.h) on the three launch shapes that reach it -- the
+team kernel with five wavefronts per CTU (one picture), the 12-search kernel with fewWaves == 1 (79 pictures) and with fewWaves == 0 (80
+pictures) -- on the clips of tests/test_simt16_host.py at QP 22 (PUs with 3, 4 and 5 candidates, one and two batches) and on the 128x128 clip
+at QP 4 (the largest levels the 16-bit columns see).  Slot 0 equals the oracle, all slots are equal; every case asserts the shape it ran."""
+import numpy as np
+import pytest
+
+import common
+import synth
+
+pytestmark = pytest.mark.gpu
+
+CLIPS = [(128, 128, 10, 1, 22), (128, 128, 10, 1, 4), (80, 80, 10, 3, 22), (192, 128, 8, 11, 22)]     # width, height, bit depth, seed of synth.frame, QP
+SHAPES = [(1, "team", 1, 5), (79, "search12", 1, 12), (80, "search12", 0, 12)]                          # pictures, kernel, fewWaves, wavefronts
+
+_want = {}
+def reference(clip):
+    """oracle.compress of a clip, computed once and shared by the three launch shapes"""
+    import oracle
+    if clip not in _want:
+        w, h, bd, seed, qp = clip
+        planes = synth.frame(w, h, bd, 0, seed)
+        _want[clip] = (planes,) + tuple(oracle.compress(planes, bd, qp, 1))
+    return _want[clip]
+
+
+@pytest.mark.parametrize("n,kernel,few,waves", SHAPES)
+@pytest.mark.parametrize("clip", CLIPS, ids=lambda c: f"{c[0]}x{c[1]}_{c[2]}b_qp{c[4]}")
+def test_hip_16x16_first_pass_matches_oracle(built, clip, n, kernel, few, waves):
+    import hm355
+    w, h, bd, seed, qp = clip
+    planes, want_rec, want_ctus = reference(clip)
+    enc = hm355.Encoder(w, h, bd, 1, max_batch=n)
+    res = enc.compress([planes] * n, qp)
+    s = enc.last_launch_shape()
+    enc.close()
+    assert (s["kernel"], s["few_waves"], s["tickets"], s["waves"]) == (kernel, few, n * len(want_ctus), waves), s
+    rec0, ctus0, stats0 = res[0]
+    common.assert_ctus_equal(ctus0, want_ctus, f"{n} pictures, slot 0", (w, h))
+    for c in range(3):
+        assert np.array_equal(rec0[c], want_rec[c]), f"{n} pictures, slot 0: reconstruction plane {c}"
+    for k in range(1, n):
+        common.assert_ctus_equal(res[k][1], ctus0, f"{n} pictures, slot {k} vs slot 0")
+        for c in range(3):
+            assert np.array_equal(res[k][0][c], rec0[c]), f"{n} pictures, slot {k}: reconstruction plane {c}"
+        assert res[k][2] == stats0, f"{n} pictures, slot {k}: picture totals"
