@@ -179,6 +179,12 @@ LDP_LONG_CASES = ["ldp2gop_256x128_8b_qp34"]     # I + two low-delay GOPs: refer
 DBK_CASES = ["dbk_ldp_200x136_8b_qp30", "dbk_ldb_192x128_10b_qp34"]    # SAO off: 'F' record = deblocked 'S' record
 
 
+# the ends of the QP range (slice QPs 0..5, 13..16 around deblocking's beta == 0, 45..51) and of the merge list (MaxNumMergeCand 1 / 2 / 3, TMVPMode 0),
+# loop filters on: tests/gen_golden.py EDGE_CASES; test_edge_fixtures_cover_what_they_are_for (tests/test_oracle_golden.py) says what each one holds
+EDGE_CASES = ["edge_ldp_136x72_8b_qp0", "edge_ldb_136x72_10b_qp2", "edge_ldp_136x72_8b_qp13", "edge_ldp_200x136_8b_qp51", "edge_ldp_200x136_8b_qp45",
+              "edge_ldb_200x136_10b_qp46", "edge_ra_192x128_8b_mrg2_notmvp", "edge_ldb_136x72_8b_mrg1", "edge_ldp_200x136_10b_mrg3"]
+
+
 def split_fixture_ctus(want):
     """fixture CTU records (tests/hmd2.py CTU_DT) -> (ctus, ictus) arrays in the C-ABI / oracle layouts"""
     import hm355

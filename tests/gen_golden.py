@@ -3,7 +3,7 @@
 reference.  The fixtures are data (inputs are regenerated from the seeded generator, expected outputs
 are stored); no reference source text is stored.
 
-    python tests/gen_golden.py
+    python tests/gen_golden.py                 (--edge-only: the EDGE_CASES alone)
 """
 import os
 import struct
@@ -130,6 +130,19 @@ LDP_CASES = [
     ("rc2_i_256x192_10b", 256, 192, 10, 3, 32, 57, 0, "encoder_intra_main10.cfg", ("--RateControl=1", "--TargetBitrate=3000000", "--LCULevelRateControl=1", "--InitialQP=28")),
     ("rc2_ra_192x128_10b", 192, 128, 10, 5, 32, 58, 0, "encoder_randomaccess_main10.cfg", ("--RateControl=1", "--TargetBitrate=300000", "--LCULevelRateControl=1", "--InitialQP=30")),
 ]
+# the ends of the QP range and of the merge list: slice QPs 0..5 (levels above 500), 13..16 (deblocking's beta == 0 below 16), 45..51 (the end of
+# the tc table, nearly empty substreams), MaxNumMergeCand 1 / 2 / 3 and TMVPMode 0; the loop filters run in all of them
+EDGE_CASES = [
+    ("edge_ldp_136x72_8b_qp0", 136, 72, 8, 4, 0, 64),
+    ("edge_ldb_136x72_10b_qp2", 136, 72, 10, 4, 2, 63, 0, "encoder_lowdelay_main10.cfg"),
+    ("edge_ldp_136x72_8b_qp13", 136, 72, 8, 4, 13, 64),
+    ("edge_ldp_200x136_8b_qp51", 200, 136, 8, 4, 51, 3),
+    ("edge_ldp_200x136_8b_qp45", 200, 136, 8, 4, 45, 4, 1),
+    ("edge_ldb_200x136_10b_qp46", 200, 136, 10, 4, 46, 12, 0, "encoder_lowdelay_main10.cfg"),
+    ("edge_ra_192x128_8b_mrg2_notmvp", 192, 128, 8, 5, 30, 65, 0, "encoder_randomaccess_main.cfg", ("--MaxNumMergeCand=2", "--TMVPMode=0")),
+    ("edge_ldb_136x72_8b_mrg1", 136, 72, 8, 4, 28, 66, 1, "encoder_lowdelay_main.cfg", ("--MaxNumMergeCand=1",)),
+    ("edge_ldp_200x136_10b_mrg3", 200, 136, 10, 4, 36, 67, 0, "encoder_lowdelay_P_main10.cfg", ("--MaxNumMergeCand=3",)),
+]
 S_KEYS = ("poc", "slice_type", "qp", "lambda", "sqrt_lambda", "weight_cb", "weight_cr", "lambda_motion_sad", "lambda_motion_sse",
           "col_from_l0", "col_ref_idx", "tmvp", "mvd_l1_zero", "max_merge_cand", "check_ldc", "cabac_init_type")
 
@@ -212,13 +225,17 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     if "--yuvio-only" in sys.argv:
         gen_yuvio(); sys.exit(0)
+    if "--edge-only" in sys.argv:
+        for c in EDGE_CASES:
+            run_ldp_case(*c)
+        sys.exit(0)
     if "--ldp-only" not in sys.argv:
         gen_kat(); gen_yuvio()
     if "--kat-only" not in sys.argv:
         if "--ldp-only" not in sys.argv:
             for c in CASES:
                 run_case(*c)
-        for c in LDP_CASES:
+        for c in LDP_CASES + EDGE_CASES:
             if "--only" in sys.argv and c[0] != sys.argv[sys.argv.index("--only") + 1]:
                 continue
             run_ldp_case(*c)

@@ -109,6 +109,40 @@ def test_hip_p_slice_batches_at_few_waves_0_match_reference_fixture(hm):
     enc.close()
 
 
+@pytest.mark.parametrize("name,slice_type", [("edge_ldp_136x72_8b_qp0", 1), ("edge_ldb_136x72_10b_qp2", 0)])
+def test_hip_low_qp_slice_batches_at_few_waves_0_match_reference_fixture(hm, name, slice_type):
+    """The three P slices of the QP-0 clip and the three B slices of the 10-bit QP-2 clip (slice QPs 2..5, levels of several hundred in the inter
+    pictures), each with its own references, in one batch of 1,280 jobs: without WaveFrontSynchro a picture offers one CTU at a time, so this is the
+    smallest batch hm355_plan_launch gives Params::fewWaves == 0, and past 1,024 streams it runs on the 12-search kernel -- the large levels go
+    through its lane code.  The first copy of each slice equals the reference's fixture; every other copy equals the first."""
+    cfg, slices, finals = common.load_ldp_case(name)
+    w, h, bd, n = cfg["width"], cfg["height"], cfg["bit_depth"], 1280
+    assert cfg["wpp"] == 0
+    ps = [r for r in slices if int(r["slice_type"]) == slice_type]
+    assert len(ps) == 3 and len(slices) == 4
+    base = []
+    for r in ps:
+        sp, refs = common.ldp_slice_inputs(r, finals)           # one ref_pics dict per POC, shared by its copies: uploaded once
+        base.append((synth.frame(w, h, bd, int(r["poc"]), cfg["seed"]), sp, refs))
+    enc = hm.Encoder(w, h, bd, 0, max_batch=n)
+    got = enc.compress_inter_batch([base[k % 3] for k in range(n)])
+    _assert_shape(enc, "search12", 0, n * enc.num_ctus)
+    enc.close()
+    for k in range(3):
+        rec, ctus, ictus, stats = got[k]
+        r = ps[k]
+        common.assert_inter_ctus_equal(ctus, ictus, r["ctus"], f"job {k} (POC {int(r['poc'])})")
+        for c in range(3):
+            assert np.array_equal(rec[c], r["rec"][c]), f"job {k}: reconstruction plane {c}"
+        assert stats[0] == int(ctus["total_bits"].sum())
+    for k in range(3, n):
+        first = got[k % 3]
+        assert got[k][1].tobytes() == first[1].tobytes() and got[k][2].tobytes() == first[2].tobytes(), f"job {k} differs from job {k % 3}"
+        for c in range(3):
+            assert np.array_equal(got[k][0][c], first[0][c]), f"job {k}: reconstruction plane {c} differs from job {k % 3}"
+        assert got[k][3] == first[3], f"job {k}: picture totals"
+
+
 def test_hip_b_slice_batch_under_wpp_at_few_waves_0_matches_oracle(built, hm):
     """A B slice under WaveFrontSynchro (192x136, 10 bit, two pictures per list, built as in test_hip_inter_matches_oracle_on_fresh_inputs), 100 copies
     in one batch: 12-search kernel at fewWaves == 0; job 0 equals the oracle, all jobs are equal, some partition is bi-predicted."""

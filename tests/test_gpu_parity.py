@@ -71,7 +71,7 @@ def _p_and_b_slices_match_reference_fixture(hm, name):
 
 
 @pytest.mark.parametrize("team", ["0", "1"])
-@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES)
+@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES + common.EDGE_CASES)
 def test_hip_p_and_b_slices_match_reference_fixture(hm, monkeypatch, name, team):
     """low-delay P, random access and low-delay B clips against the reference fixture (see _p_and_b_slices_match_reference_fixture) --
     searched by one wavefront per CTU (team 0) and by a team of wavefronts per CTU (team 1, hm355_team.h: what a one-picture launch gets)."""
@@ -79,7 +79,7 @@ def test_hip_p_and_b_slices_match_reference_fixture(hm, monkeypatch, name, team)
     _p_and_b_slices_match_reference_fixture(hm, name)
 
 
-@pytest.mark.parametrize("name", ["ldp_200x136_8b_qp24", "ldb_200x136_8b_qp30"])
+@pytest.mark.parametrize("name", ["ldp_200x136_8b_qp24", "ldb_200x136_8b_qp30", "edge_ldb_136x72_10b_qp2", "edge_ldb_136x72_8b_mrg1"])
 def test_hip_p_and_b_slices_with_five_wavefront_teams_match_reference_fixture(hm, monkeypatch, name):
     """a P / B launch searched by teams of five wavefronts (HM355_TEAM_WAVES=5: no partners, compress_cu_inter_modes_duo hands the whole candidate
     chain of a CU to compress_cu_inter_modes on the wavefront that has it) on one P and one B clip with boundary CUs: the same fixture, bit-exact."""
@@ -208,7 +208,7 @@ def test_hip_deblocking_matches_reference(hm, name):
     enc.close()
 
 
-@pytest.mark.parametrize("name", common.DBK_CASES + [common.LDP_CASES[0], common.B_CASES[0]])
+@pytest.mark.parametrize("name", common.DBK_CASES + [common.LDP_CASES[0], common.B_CASES[0]] + common.EDGE_CASES)
 def test_hip_closed_loop_on_device_matches_reference(hm, name):
     """A whole clip on the device, no host round trip of pictures between frames: search -> deblock in place -> device-resident
     reference (border extension + compressMotion on the device) -> next picture's search.  Clips the reference ran with SAO off compare
@@ -366,7 +366,7 @@ def test_full_size_pictures_match_reference_digests(hm, name):
     enc.close()
 
 
-@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES + common.DBK_CASES + common.LDP_LONG_CASES)
+@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES + common.DBK_CASES + common.LDP_LONG_CASES + common.EDGE_CASES)
 def test_hip_bitstream_pass_matches_reference(hm, name):
     """hm355_encode_slice (host buffers in) on the reference's own CTU decisions and SAO parameters: the substream bytes, the bin count and
     the context table choice for the next picture must equal what the reference's TEncSlice::encodeSlice produced (I, P and B slices,

@@ -137,7 +137,10 @@ def test_hostsim_of_kernel_source_matches_oracle_at_extreme_qps(tmp_path):
         common.assert_rec_equal(want_rec, got[0][1], w, h, f"{w}x{h} qp{qp}")
 
 
-@pytest.mark.parametrize("name", common.LDP_CASES[1:] + common.B_CASES + common.LDP_LONG_CASES)
+HOSTSIM_EDGE_CASES = [n for n in common.EDGE_CASES if n.endswith(("_qp0", "_qp2", "_qp51", "_mrg2_notmvp"))]     # about 25 s each, mostly compilation
+
+
+@pytest.mark.parametrize("name", common.LDP_CASES[1:] + common.B_CASES + common.LDP_LONG_CASES + HOSTSIM_EDGE_CASES)
 def test_hostsim_of_kernel_source_matches_reference_p_slices(tmp_path, name):
     """The P-slice part of the kernel source (hm355_inter.h / hm355_inter_cu.h) compiled for the host with one lane, forwards and
     with every lane-parallel loop reversed: self-checking replay of the reference's HMD2 record stream (rebuilt from the fixture),

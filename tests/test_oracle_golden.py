@@ -53,11 +53,8 @@ def test_oracle_transform_kats(built):
         assert np.array_equal(got, want), f"record {r} tag {tag} n {n} bd {bd} dst {dst}"
 
 
-@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES)
-def test_oracle_matches_reference_p_and_b_slices(built, name):
-    """encoder_lowdelay_P_main.cfg / encoder_randomaccess_main10.cfg / encoder_lowdelay_main.cfg: every P or B slice of the clip,
-    with the reference pictures (final reconstruction + motion field) and slice parameters exactly as the reference's
-    compressSlice saw them; decisions, motion, coefficients, costs and the pre-deblocking reconstruction must match bit for bit."""
+def _check_p_and_b_slices(name):
+    """every P / B slice of clip `name` through the oracle, against the fixture; returns the number of slices compared"""
     import oracle
     cfg, slices, finals = common.load_ldp_case(name)
     n_p = 0
@@ -70,7 +67,21 @@ def test_oracle_matches_reference_p_and_b_slices(built, name):
         for c in range(3):
             assert np.array_equal(rec[c], r["rec"][c]), f"{name} POC {int(r['poc'])}: reconstruction plane {c}"
         n_p += 1
-    assert n_p >= 3
+    return n_p
+
+
+@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES)
+def test_oracle_matches_reference_p_and_b_slices(built, name):
+    """encoder_lowdelay_P_main.cfg / encoder_randomaccess_main10.cfg / encoder_lowdelay_main.cfg: every P or B slice of the clip,
+    with the reference pictures (final reconstruction + motion field) and slice parameters exactly as the reference's
+    compressSlice saw them; decisions, motion, coefficients, costs and the pre-deblocking reconstruction must match bit for bit."""
+    assert _check_p_and_b_slices(name) >= 3
+
+
+@pytest.mark.parametrize("name", common.EDGE_CASES)
+def test_oracle_matches_reference_p_and_b_slices_at_the_edges(built, name):
+    """the same comparison over the edge clips: slice QPs 0..5, 13..16 and 45..51, MaxNumMergeCand 1 / 2 / 3, TMVPMode 0"""
+    assert _check_p_and_b_slices(name) >= 3
 
 
 @pytest.mark.parametrize("name", common.DBK_CASES)
@@ -88,16 +99,14 @@ def test_oracle_deblocking_matches_reference(built, name):
         assert any(not np.array_equal(r["rec"][c], want[c]) for c in range(3)), "the fixture does not exercise the filter"
 
 
-@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES)
-def test_oracle_sao_matches_reference(built, name):
-    """TEncSampleAdaptiveOffset::SAOProcess: deblocking + SAO of the oracle on the pre-deblocking reconstruction must give the reference's
-    finished picture, the same per-CTU SAO parameters and the same slice-level enable flags for every picture of the clip (the
-    picture-level on/off rule carries the disabled rates from picture to picture)."""
+def _check_deblock_and_sao(name):
+    """deblocking + SAO of the oracle over every picture of clip `name`, the disabled rates carried from picture to picture, against the
+    fixture's finished pictures, SAO parameters and slice-level flags; returns ({poc: the oracle's deblocked planes}, blocks with new offsets)"""
     import oracle
     saod = {}
     cfg, slices, finals = common.load_ldp_case(name, sao=saod)
     rate = np.zeros((3, 8), np.float64)
-    n_new = 0
+    n_new, deblocked = 0, {}
     for r in slices:
         poc = int(r["poc"])
         ctus, ictus = common.split_fixture_ctus(r["ctus"])
@@ -110,7 +119,115 @@ def test_oracle_sao_matches_reference(built, name):
         for c in range(3):
             assert np.array_equal(out[c], finals[poc]["rec"][c]), f"{name} POC {poc}: finished picture plane {c}"
         n_new += int((a["sao"][:, :, 0] == 1).sum())
+        deblocked[poc] = dbk
+    return deblocked, n_new
+
+
+@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES)
+def test_oracle_sao_matches_reference(built, name):
+    """TEncSampleAdaptiveOffset::SAOProcess: deblocking + SAO of the oracle on the pre-deblocking reconstruction must give the reference's
+    finished picture, the same per-CTU SAO parameters and the same slice-level enable flags for every picture of the clip (the
+    picture-level on/off rule carries the disabled rates from picture to picture)."""
+    _, n_new = _check_deblock_and_sao(name)
     assert n_new > 0, "the fixture never chose new offsets"
+
+
+@pytest.mark.parametrize("name", common.EDGE_CASES)
+def test_oracle_deblocking_and_sao_match_reference_at_the_edges(built, name):
+    """the same chain over the edge clips (the high-QP ones choose no new offsets: test_edge_fixtures_cover_what_they_are_for is the guard
+    against an empty comparison).  Of the clip around QP 16 the oracle's deblocking alone must leave the pictures below QP 16 as they were
+    (beta == 0) and change all three planes of the others."""
+    deblocked, _ = _check_deblock_and_sao(name)
+    if name == "edge_ldp_136x72_8b_qp13":
+        _, slices, _ = common.load_ldp_case(name)
+        for r in slices:
+            changed = [not np.array_equal(deblocked[int(r["poc"])][c], r["rec"][c]) for c in range(3)]
+            assert changed == [int(r["qp"]) >= 16] * 3, f"{name} POC {int(r['poc'])} (QP {int(r['qp'])}): planes changed by deblocking {changed}"
+
+
+# what each edge clip is for: slice QPs in coding order, (tmvp, max_merge_cand) of every slice record, largest merge_idx of the clip
+EDGE_TABLE = {
+    "edge_ldp_136x72_8b_qp0": ([0, 3, 2, 3], (1, 5), 3),
+    "edge_ldb_136x72_10b_qp2": ([2, 5, 4, 5], (1, 5), 4),
+    "edge_ldp_136x72_8b_qp13": ([13, 16, 15, 16], (1, 5), 2),
+    "edge_ldp_200x136_8b_qp51": ([51, 51, 51, 51], (1, 5), 3),
+    "edge_ldp_200x136_8b_qp45": ([45, 48, 47, 48], (1, 5), 4),
+    "edge_ldb_200x136_10b_qp46": ([46, 49, 48, 49], (1, 5), 4),
+    "edge_ra_192x128_8b_mrg2_notmvp": ([30, 32, 33, 34, 34], (0, 2), 1),
+    "edge_ldb_136x72_8b_mrg1": ([28, 31, 30, 31], (1, 1), 0),
+    "edge_ldp_200x136_10b_mrg3": ([36, 39, 38, 39], (1, 3), 2),
+}
+
+
+def test_edge_fixtures_cover_what_they_are_for():
+    """The edge clips are compared without floors on what they contain (a QP-51 clip rightly has no new SAO offsets and a hundred bytes of slice
+    data), so this test holds each of them to what it was generated for."""
+    assert sorted(EDGE_TABLE) == sorted(common.EDGE_CASES)
+    clips = {}
+    for name in common.EDGE_CASES:
+        sd, bd = {}, {}
+        cfg, slices, finals = common.load_ldp_case(name, sao=sd, bits=bd)
+        qps, (tmvp, mmc), max_idx = EDGE_TABLE[name]
+        assert [int(r["qp"]) for r in slices] == qps, name
+        assert all((int(r["tmvp"]), int(r["max_merge_cand"])) == (tmvp, mmc) for r in slices), name
+        inter = [r for r in slices if int(r["slice_type"]) != 2]
+        assert len(inter) >= 3 and int(slices[0]["slice_type"]) == 2, name
+        merged = np.concatenate([r["ctus"]["merge_idx"][r["ctus"]["merge_flag"] == 1] for r in inter])
+        assert len(merged) > 0 and int(merged.max()) == max_idx, f"{name}: largest merge_idx {int(merged.max())}"
+        clips[name] = dict(cfg=cfg, slices=slices, inter=inter, sao=sd,
+                           # per picture in coding order: blocks with new SAO offsets, samples per plane the loop filters changed, bytes per substream
+                           new={int(r["poc"]): int((sd[int(r["poc"])]["sao"][:, :, 0] == 1).sum()) for r in slices},
+                           changed={int(r["poc"]): [int((r["rec"][c] != finals[int(r["poc"])]["rec"][c]).sum()) for c in range(3)] for r in slices},
+                           sizes={int(r["poc"]): [len(x) for x in bd[int(r["poc"])]["substreams"]] for r in slices})
+
+    def level(rs):
+        return max(int(np.abs(r["ctus"][f]).max()) for r in rs for f in ("coeff_y", "coeff_cb", "coeff_cr"))
+
+    def pocs(rs):
+        return [int(r["poc"]) for r in rs]
+    # the two low-QP clips: levels of 500 and more (the I pictures), levels beyond 8 bits in the P / B pictures; inert loop filters in the QP-0 P pictures
+    for name in ("edge_ldp_136x72_8b_qp0", "edge_ldb_136x72_10b_qp2"):
+        c = clips[name]
+        assert level(c["slices"]) >= 500 and level(c["inter"]) > 255, name
+        assert all(sum(c["sizes"][p]) > 2000 for p in pocs(c["slices"])), name
+    c = clips["edge_ldp_136x72_8b_qp0"]
+    assert all(c["changed"][p] == [0, 0, 0] for p in pocs(c["inter"]))
+    c = clips["edge_ldb_136x72_10b_qp2"]
+    assert all(c["new"][p] > 0 for p in pocs(c["slices"])), "SAO new offsets in every picture"
+    # B clips: bi-prediction in every B slice, and mvd_l1_zero in the low-delay ones
+    for name in ("edge_ldb_136x72_10b_qp2", "edge_ldb_200x136_10b_qp46", "edge_ra_192x128_8b_mrg2_notmvp", "edge_ldb_136x72_8b_mrg1"):
+        c = clips[name]
+        assert all(int(r["slice_type"]) == 0 and (r["ctus"]["inter_dir"] == 3).any() for r in c["inter"]), name
+        if "_ldb_" in name:
+            assert all(int(r["mvd_l1_zero"]) == 1 for r in c["inter"]), name
+    c = clips["edge_ra_192x128_8b_mrg2_notmvp"]               # references in both directions
+    assert any(r["ref_poc"][0][0] < int(r["poc"]) < r["ref_poc"][1][0] for r in c["inter"])
+    # around beta == 0.  The I picture (QP 13) chose new SAO offsets, so its finished picture says nothing about deblocking alone (the oracle's
+    # deblocking, which test_oracle_deblocking_and_sao_match_reference_at_the_edges chains to the finished picture, leaves it unchanged); the QP-15
+    # picture has SAO off and is left exactly as reconstructed; the QP-16 pictures change in all three planes
+    c = clips["edge_ldp_136x72_8b_qp13"]
+    for r in c["slices"]:
+        p, ch = int(r["poc"]), c["changed"][int(r["poc"])]
+        if int(r["qp"]) == 15:
+            assert ch == [0, 0, 0] and c["sao"][p]["enabled"] == (0, 0)
+        elif int(r["qp"]) == 16:
+            assert all(v > 0 for v in ch)
+        else:
+            assert c["new"][p] > 0
+    # the high-QP clips: no new SAO offsets, thousands of deblocked luma samples in the I picture, P / B pictures of a few bytes
+    for name in ("edge_ldp_200x136_8b_qp51", "edge_ldp_200x136_8b_qp45", "edge_ldb_200x136_10b_qp46"):
+        c = clips[name]
+        assert all(c["new"][p] == 0 for p in pocs(c["slices"])), name
+        assert c["changed"][0][0] > 6000 and all(c["changed"][p][0] > 500 for p in pocs(c["inter"])), name
+        assert all(sum(c["sizes"][p]) < 40 for p in pocs(c["inter"])), name
+        assert all((r["ctus"]["skip"] == 1).any() for r in c["inter"]), name
+    c = clips["edge_ldp_200x136_8b_qp51"]
+    assert c["changed"][0][0] == 6540 and all(8 <= sum(c["sizes"][p]) <= 10 for p in pocs(c["inter"]))
+    c = clips["edge_ldp_200x136_8b_qp45"]                    # WPP: three substreams per picture, some shorter than 8 bytes
+    sizes = [c["sizes"][p] for p in pocs(c["slices"])]
+    assert c["cfg"]["wpp"] == 1 and all(len(v) == 3 for v in sizes) and sum(1 for v in sizes for b in v if b < 8) >= 3, sizes
+    c = clips["edge_ldb_136x72_8b_mrg1"]                     # WPP with one merge candidate: merge_idx is never coded
+    assert c["cfg"]["wpp"] == 1 and all(len(c["sizes"][p]) == 2 for p in pocs(c["slices"]))
 
 
 def fixture_bits_args(cfg, r, sao_rec, with_sao):
@@ -119,11 +236,9 @@ def fixture_bits_args(cfg, r, sao_rec, with_sao):
                 max_merge_cand=int(r["max_merge_cand"]), sao=sao_rec["sao"] if with_sao else None, sao_enabled=tuple(sao_rec["enabled"]) if with_sao else (0, 0))
 
 
-@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES + common.DBK_CASES + common.LDP_LONG_CASES)
-def test_oracle_bitstream_pass_matches_reference(built, name):
-    """TEncSlice::encodeSlice: from the reference's own CTU decisions and SAO parameters the oracle's arithmetic coder must write the same
-    substream bytes as the reference (I, P and B slices, 8 and 10 bit, one substream or one per CTU row, SAO syntax on and off), code the
-    same number of bins and leave the same context table choice for the next picture (determineCabacInitIdx)."""
+def _check_bitstream_pass(name):
+    """the oracle's arithmetic coder on the fixture's CTU decisions and SAO parameters of every picture of clip `name`: substream bytes, bins,
+    next context table; returns the bytes of slice data compared"""
     import oracle
     sd, bd = {}, {}
     cfg, slices, _ = common.load_ldp_case(name, sao=sd, bits=bd)
@@ -140,7 +255,22 @@ def test_oracle_bitstream_pass_matches_reference(built, name):
             assert g == w, f"{name} POC {poc}: substream {k} differs ({len(g)} vs {len(w)} bytes)"
         assert bins == want["num_bins"] and nxt == want["next_cabac_init_type"], f"{name} POC {poc}: bins {bins}/{want['num_bins']}, next table {nxt}/{want['next_cabac_init_type']}"
         total += sum(len(s) for s in subs)
-    assert total > 500
+    return total
+
+
+@pytest.mark.parametrize("name", common.LDP_CASES + common.B_CASES + common.DBK_CASES + common.LDP_LONG_CASES)
+def test_oracle_bitstream_pass_matches_reference(built, name):
+    """TEncSlice::encodeSlice: from the reference's own CTU decisions and SAO parameters the oracle's arithmetic coder must write the same
+    substream bytes as the reference (I, P and B slices, 8 and 10 bit, one substream or one per CTU row, SAO syntax on and off), code the
+    same number of bins and leave the same context table choice for the next picture (determineCabacInitIdx)."""
+    assert _check_bitstream_pass(name) > 500
+
+
+@pytest.mark.parametrize("name", common.EDGE_CASES)
+def test_oracle_bitstream_pass_matches_reference_at_the_edges(built, name):
+    """the same comparison over the edge clips: levels above 500, substreams of a few bytes, merge_idx with one, two and three candidates
+    (the QP-51 clip writes about a hundred bytes in all, so there is no floor on the size here)"""
+    assert _check_bitstream_pass(name) > 0
 
 
 @pytest.mark.parametrize("name", common.YUVIO_CASES)
