@@ -260,7 +260,7 @@ struct Lane {           // one launch of the search in flight: its own stream, s
   DevBuf<WorkItem> dItems; // the work list, grown to the longest one so far
   DevBuf<unsigned int> dSched; // [0] ticket, [1] abort, [2] CTUs published by the launch (the spin timeout watches it); lane 0: [8] ticket, [9] abort of the bitstream launch
   std::vector<WorkItem> items; std::vector<int> stepStart; std::vector<FrameBuf> fbs;
-  long long key[5] = {}; int keyValid = 0, fewWaves = -1, fast = 0;   // fewWaves, fast: the values dP holds (-1: dP not written yet; fast = esd | cfm << 1 | ecu << 2)
+  long long key[5] = {}; int keyValid = 0, fewWaves = -1, fast = 0;   // fewWaves, fast: the values dP holds (-1: dP not written yet; fast = esd | cfm << 1 | ecu << 2 | the motion search from bit 3)
   int busy = 0, grid = 0, inFixup = 0, prepared = 0;   // prepared: the launch ran on slots an open slice prepared (hm355_run_ctus)
   DevBuf<Pel> dTeamWin; size_t teamCap = 0;   // team launches (hm355_team.h): the helpers' reconstruction windows, for teamCap teams
   ~Lane() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (stream) (void)hipStreamDestroy(stream); }
@@ -332,6 +332,7 @@ extern "C" int hm355_create(const hm355_seq_cfg *cfg, hm355_ctx **out)
   P.width = cfg->width; P.height = cfg->height; P.bitDepth = cfg->bit_depth; P.wpp = cfg->wavefront_synchro;
   P.wCtu = (cfg->width + 63) / 64; P.hCtu = (cfg->height + 63) / 64;
   P.stride[0] = P.wCtu * 64; P.stride[1] = P.stride[2] = P.wCtu * 32;
+  P.fullSearch = 0; P.searchRange = 64; P.bipredRange = 4;      // hm355_set_motion_search's defaults: FastSearch 1, SearchRange 64, BipredSearchRange 4
   c->numCtus = P.wCtu * P.hCtu;
   *out = c;   // from here on the caller destroys on failure
   { const int rc = lane_init(c, 0); if (rc != HM355_OK) return rc; }
@@ -372,7 +373,7 @@ extern "C" int hm355_create(const hm355_seq_cfg *cfg, hm355_ctx **out)
   P.prof = c->prof;
 #endif
   HM_CHECK(c, hipMemcpy(c->lane[0].dP, &P, sizeof(Params), hipMemcpyHostToDevice));
-  c->lane[0].fewWaves = P.fewWaves;
+  c->lane[0].fewWaves = P.fewWaves; c->lane[0].fast = P.bipredRange << 4 | P.searchRange << 12;
   return HM355_OK;
 }
 
@@ -488,7 +489,9 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   // the launch shape (hm355_plan_launch, hm355_host_common.h: which kernel, how many workgroups, Params::fewWaves)
   int anyInter = 0;
   for (int f = 0; f < n; f++) if (c->slots[slot0 + f].fb.imeta) anyInter = 1;
-  const int fast = P.esd | P.cfm << 1 | P.ecu << 2;
+  // what a lane's Params must follow: the switches, full search (bit 3) and the ranges above it.  The planner sees bits 0..3: to it full search
+  // is one more switch that rules teams out (hm355_host_common.h)
+  const int fastKey = P.esd | P.cfm << 1 | P.ecu << 2 | P.fullSearch << 3 | P.bipredRange << 4 | P.searchRange << 12, fast = fastKey & 15;
   int envTeam = -1, envTeamWaves = 0;
   { const char *ev = getenv("HM355_TEAM"); if (ev && (ev[0] == '0' || ev[0] == '1')) envTeam = ev[0] - '0'; }
   { const char *ev = getenv("HM355_TEAM_WAVES"); if (ev) envTeamWaves = atoi(ev); }
@@ -503,12 +506,12 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     plan = hm355_plan_launch(P.wCtu, P.hCtu, P.wpp, c->cfg.max_batch, n, ctu0, ctu1, anyInter, fast, envTeam, envTeamWaves, c->laneShare, (long long)L.teamCap);
   }
   const int fewWaves = plan.fewWaves, waves = plan.waves;
-  if (fewWaves != L.fewWaves || fast != L.fast) {
+  if (fewWaves != L.fewWaves || fastKey != L.fast) {
     Params lp = c->hp; lp.ws = L.dWs; lp.fewWaves = fewWaves; lp.teamWin = L.dTeamWin; lp.teamWinStride = winSamples;
     if (l == 0) { c->hp.fewWaves = fewWaves; c->hp.teamWin = L.dTeamWin; c->hp.teamWinStride = winSamples; }
     HM_CHECK(c, hipMemcpyAsync(L.dP, &lp, sizeof(Params), hipMemcpyHostToDevice, L.stream));
     HM_CHECK(c, hipStreamSynchronize(L.stream));      // lp is a local
-    L.fewWaves = fewWaves; L.fast = fast;
+    L.fewWaves = fewWaves; L.fast = fastKey;
   }
   next_epoch(c);
   HM_CHECK(c, hipMemsetAsync(L.dSched, 0, 32, L.stream));       // ticket = 0, abort = 0, published CTUs = 0 (+ the counters of diagnostic builds)
@@ -632,6 +635,17 @@ extern "C" int hm355_set_fast_decisions(hm355_ctx *c, int esd, int cfm, int ecu)
   for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_fast_decisions: a slice is open (hm355_slice_end first)");
   for (int l = 0; l < HM_MAX_LANES; l++) if (c->lane[l].busy) return fail(c, HM355_ERR_ARG, "hm355_set_fast_decisions: a launch is in flight (hm355_run_wait first)");
   c->hp.esd = esd; c->hp.cfm = cfm; c->hp.ecu = ecu;
+  return HM355_OK;
+}
+extern "C" int hm355_set_motion_search(hm355_ctx *c, int fast_search, int search_range, int bipred_search_range)
+{
+  if (!c) return HM355_ERR_ARG;
+  if (fast_search != 0 && fast_search != 1) return fail(c, HM355_ERR_ARG, "hm355_set_motion_search: fast_search is 0 (full search) or 1 (TZ); the selective TZ search (FastSearch=2) is not built");
+  if (search_range < 1 || search_range > 256) return fail(c, HM355_ERR_ARG, "hm355_set_motion_search: search_range is 1..256");
+  if (bipred_search_range < 1 || bipred_search_range > 16) return fail(c, HM355_ERR_ARG, "hm355_set_motion_search: bipred_search_range is 1..16");
+  for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_motion_search: a slice is open (hm355_slice_end first)");
+  for (int l = 0; l < HM_MAX_LANES; l++) if (c->lane[l].busy) return fail(c, HM355_ERR_ARG, "hm355_set_motion_search: a launch is in flight (hm355_run_wait first)");
+  c->hp.fullSearch = !fast_search; c->hp.searchRange = search_range; c->hp.bipredRange = bipred_search_range;
   return HM355_OK;
 }
 extern "C" int hm355_run_wait(hm355_ctx *c, int lane, double *kernel_ms)

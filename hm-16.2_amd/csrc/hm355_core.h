@@ -299,9 +299,9 @@ struct TZ {                            // state of one integer motion search (In
   const Pel *org; int orgStride, w, h;
   const Pel *ref; int refStride;
   uint32_t bestSad; int bestX, bestY, bestDist, bestRound, pointNr;
-  int16_t l, r, t, b;                  // search range in integer samples (within +-64 of a clipped vector: 16 bits are plenty)
+  int16_t l, r, t, b;                  // search range in integer samples (within +-256 of a clipped vector: 16 bits are plenty)
   int16_t subShift, pad_;
-  int16_t lx[16], ly[16]; int8_t lp[16], ld[16];   // search points queued for one batched evaluation (x, y, point number, distance)
+  int16_t lx[16], ly[16]; uint16_t lpd[16];        // search points queued for one batched evaluation (x, y, point number 0..8 | distance 0..256 << 4)
   int16_t wx0, wy0, ww, wh;            // reference window staged in LDS (tz_stage_window): origin in search-point coordinates, size in samples; ww == 0: none
 };
 struct IrqFrame {                      // one level of the inter residual quadtree (xEstimateResidualQT)

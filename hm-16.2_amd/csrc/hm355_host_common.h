@@ -158,7 +158,7 @@ struct hm355_launch_plan {
   int grid, groups;                         // ... or hm355_ctu_kernel with `groups` workgroups of HM_CTU_WAVES searches (grid = groups * HM_CTU_WAVES)
 };
 // n pictures of wCtu x hCtu CTUs, CTUs [ctu0, ctu1] of each, on a context created with max_batch and WaveFrontSynchro = wpp.  anyInter: a P / B slice
-// among them; fast: esd | cfm << 1 | ecu << 2; envTeam: HM355_TEAM (-1 unset, 0, 1); envTeamWaves: HM355_TEAM_WAVES (0 unset); laneShare:
+// among them; fast: esd | cfm << 1 | ecu << 2 | full search << 3; envTeam: HM355_TEAM (-1 unset, 0, 1); envTeamWaves: HM355_TEAM_WAVES (0 unset); laneShare:
 // hm355_set_lane_share; teamCap: teams the lane's reconstruction windows exist for (the caller grows them to `want` and plans again).
 static inline hm355_launch_plan hm355_plan_launch(int wCtu, int hCtu, int wpp, int maxBatch, int n, int ctu0, int ctu1, int anyInter, int fast,
                                                   int envTeam, int envTeamWaves, int laneShare, long long teamCap)
@@ -179,6 +179,9 @@ static inline hm355_launch_plan hm355_plan_launch(int wCtu, int hCtu, int wpp, i
   if (envTeam == 1 && p.wsCount >= HM_TEAM) useTeam = 1;
   // hm355_set_fast_decisions: the team protocol starts sub-CUs and partner candidates speculatively, which is not valid once candidates or
   // sub-CUs may be cut short -- a P / B launch with any of the switches on is searched by one wavefront per CTU, whatever HM355_TEAM says
+  // hm355_set_motion_search with fast_search 0 (bit 3 of `fast`): the same.  The protocol's token pass (me_token_prepass) repeats the 2Nx2N integer
+  // search only to hand m_integerMv2Nx2N on; the full search neither reads nor writes it, and an exhaustive search run twice for nothing
+  // costs more than the team saves.
   if (anyInter && fast) useTeam = 0;
   p.waves = anyInter ? HM_TEAM : HM_TEAM_I;   // P / B slices: every chain of candidates on two or three wavefronts (hm355_team.h)
   if (envTeamWaves == HM_TEAM_I) p.waves = HM_TEAM_I;   // A/B runs (five-wavefront teams on P streams: 1,021 / 1,529 / 1,871 CTU/s in the table above)

@@ -456,7 +456,7 @@ HM_DEV inline void tz_stage_window(Shared *e, TZ *z, int cx, int cy, int R)
   z->wx0 = (int16_t)x0; z->wy0 = (int16_t)y0; z->ww = (int16_t)ww; z->wh = (int16_t)wh;
   HM_SYNC();
 }
-#define TZ_PUSH(z, n, X, Y, PN, D) do { (z)->lx[n] = (int16_t)(X); (z)->ly[n] = (int16_t)(Y); (z)->lp[n] = (int8_t)(PN); (z)->ld[n] = (int8_t)(D); (n)++; } while (0)
+#define TZ_PUSH(z, n, X, Y, PN, D) do { (z)->lx[n] = (int16_t)(X); (z)->ly[n] = (int16_t)(Y); (z)->lpd[n] = (uint16_t)((PN) | (D) << 4); (n)++; } while (0)
 HM_DEV HM_NOINLINE void tz_eval_list(Shared *e, int n)
 {
   HM_ENTRY(e); n = HM_UNI(n);
@@ -536,7 +536,7 @@ HM_DEV HM_NOINLINE void tz_eval_list(Shared *e, int n)
   best = 0x7fffffff - hm_wave_max_i(0x7fffffff - vCost);
   bestPnt = (int)(__builtin_ctzll(__ballot(vCost == best))) / L;
 #endif
-  if ((uint32_t)best < z->bestSad) { z->bestSad = (uint32_t)best; z->bestX = z->lx[bestPnt]; z->bestY = z->ly[bestPnt]; z->bestDist = z->ld[bestPnt]; z->bestRound = 0; z->pointNr = z->lp[bestPnt]; }
+  if ((uint32_t)best < z->bestSad) { z->bestSad = (uint32_t)best; z->bestX = z->lx[bestPnt]; z->bestY = z->ly[bestPnt]; z->bestDist = z->lpd[bestPnt] >> 4; z->bestRound = 0; z->pointNr = z->lpd[bestPnt] & 15; }
   HM_SYNC();
 }
 HM_DEV inline void tz_help(Shared *e, int sx, int sy, int pointNr, int dist)
@@ -609,9 +609,13 @@ HM_DEV inline void set_search_range(const Shared *e, MvD pred, int rng, int cuX,
   a = clip_mv(e, a, cuX, cuY); b = clip_mv(e, b, cuX, cuY);
   lt->x = a.x >> 2; lt->y = a.y >> 2; rb->x = b.x >> 2; rb->y = b.y >> 2;
 }
+// hm355_set_motion_search: SearchRange / BipredSearchRange of the launch (TEncSearch::m_iSearchRange, m_bipredSearchRange; ASR is not built, so
+// m_aaiAdaptSR[list][ref] is SearchRange everywhere).  A zero in Params is the reference's default.
+HM_DEV inline int me_search_range(const Shared *e) { const int v = HM_UNI(e->P->searchRange); return v ? v : 64; }
+HM_DEV inline int me_bipred_range(const Shared *e) { const int v = HM_UNI(e->P->bipredRange); return v ? v : 4; }
 HM_DEV inline uint32_t tz_search(Shared *e, TZ *z, MvD *mv, int cuX, int cuY, MvD lt, MvD rb, int useInt, MvD intMv2Nx2N)
 {
-  const int searchRange = 64, raster = 5;
+  const int searchRange = me_search_range(e), raster = 5;
   int rl = lt.x, rr = rb.x, rt = lt.y, rbm = rb.y;
   z->l = lt.x; z->r = rb.x; z->t = lt.y; z->b = rb.y;
   MvD c = clip_mv(e, *mv, cuX, cuY); c.x >>= 2; c.y >>= 2;
@@ -696,17 +700,100 @@ HM_DEV inline uint32_t pattern_refinement(Shared *e, TZ *z, const Pel *refAtInt,
   return best;
 }
 
-// xPatternSearch :3932-3988: full search over the (small) bi-prediction range, one point per tz_help call
-HM_DEV inline uint32_t pattern_search(Shared *e, TZ *z, MvD *mv, MvD lt, MvD rb)
+// xPatternSearch :3932-3988: full search over the (small) bi-prediction range, 16 queued points per pass
+HM_DEV inline uint32_t pattern_search(Shared *e, TZ *z, MvD *mv, MvD lt, MvD rb, int range)
 {
   z->bestSad = 0xffffffffu; z->bestX = z->bestY = 0; z->bestDist = 0; z->bestRound = 0; z->pointNr = 0; z->ww = 0;
   z->l = lt.x; z->r = rb.x; z->t = lt.y; z->b = rb.y;
-  tz_stage_window(e, z, (lt.x + rb.x) >> 1, (lt.y + rb.y) >> 1, 5);     // all 81 points from one window
+  tz_stage_window(e, z, (lt.x + rb.x) >> 1, (lt.y + rb.y) >> 1, range + 1);     // all (2 range + 1)^2 points from one window, where it fits
   int n_ = 0;
   for (int y = lt.y; y <= rb.y; y++) for (int x = lt.x; x <= rb.x; x++) { TZ_PUSH(z, n_, x, y, 0, 0); if (n_ == 16) { tz_eval_list(e, n_); n_ = 0; } }
   if (n_) tz_eval_list(e, n_);
   mv->x = (int16_t)z->bestX; mv->y = (int16_t)z->bestY;
   return z->bestSad - mc_cost32(e, mc_bits(e, z->bestX, z->bestY));
+}
+// xPatternSearch :3932-3988 over a whole SearchRange window (uni-prediction with FastSearch=0): every integer point of [l..r] x [t..b], SAD with
+// the row sub-sampling of the fast encoder setting plus the cost of the vector, the cheapest point wins and among equals the first in raster
+// order (y outer, x inner, strict "<" in the reference).
+// Candidates in lanes: a pass gives every lane one search point -- nx consecutive x of 64 / nx consecutive candidate rows, so lane order is
+// raster order -- and the lane adds up its own SAD over the block rows: no cross-lane reduction, the origin sample of a step is the same
+// address on every lane.  The window is cut into strips of at most 64 columns.  The reference rows a strip touches (nx + w - 1 samples each)
+// are staged in the transform buffers (idle during the motion search, as for tz_stage_window) in a ring of nr rows that slides down the
+// window: a row is loaded from the reference plane once per strip and read by up to h candidate rows.  Lanes with adjacent x read adjacent
+// 16-bit samples, two to a bank.  A strip whose ring cannot hold the rows of one pass (64-high PUs, 32-high ones at the widest strips) reads
+// the border-extended reference plane instead, adjacent lanes at adjacent addresses.
+// A pass ends with one wave minimum; the lowest lane that holds it is the pass's first point in raster order.  The running best is replaced
+// when the pass's winner is cheaper or equally cheap and earlier in raster order, so the result does not depend on the order of the strips.
+HM_DEV HM_NOINLINE void full_search(Shared *e)
+{
+  HM_ENTRY(e);
+  TZ *z = &e->tz;
+  const Pel *org = hm_uni_ptr(z->org), *ref = hm_uni_ptr(z->ref);
+  const int so = HM_UNI(z->orgStride), sr = HM_UNI(z->refStride), w = HM_UNI(z->w), h = HM_UNI(z->h), sub = HM_UNI(z->subShift), bd = e->bitDepth;
+  const int l = HM_UNI(z->l), r = HM_UNI(z->r), t = HM_UNI(z->t), b = HM_UNI(z->b);
+  const int rows = h >> sub, step = 1 << sub, so2 = so << sub, sr2 = sr << sub;
+  Pel *win = (Pel *)e->bufA;
+  uint32_t best = 0xffffffffu; int bestX = 0, bestY = 0;
+  z->ww = 0;
+  for (int x0 = l; x0 <= r; x0 += 64) {
+    const int nx = r - x0 + 1 < 64 ? r - x0 + 1 : 64, sw = nx + w - 1, lastRow = b + h - 1;
+    int pr = 64 / nx;                                   // candidate rows per pass
+    if (pr > b - t + 1) pr = b - t + 1;
+    int nr = HM_TZ_WIN_SAMPLES / sw;                    // rows of the ring
+    if (nr > lastRow - t + 1) nr = lastRow - t + 1;
+    const int staged = nr >= h + pr - 1;
+    int hi = t - 1;                                     // last reference row in the ring
+    for (int y0 = t; y0 <= b; y0 += pr) {
+      const int np = b - y0 + 1 < pr ? b - y0 + 1 : pr;
+      if (staged && y0 + np + h - 2 > hi) {             // rows above y0 are dead: refill their places
+        const int first = hi + 1, last = y0 + nr - 1 < lastRow ? y0 + nr - 1 : lastRow, m = last - first + 1, s0 = (first - t) % nr;
+        const Pel *src = ref + (ptrdiff_t)first * sr + x0;
+        HM_PAR_FOR_XY(x, y, sw, m * sw) { int s = s0 + y; if (s >= nr) s -= nr; win[s * sw + x] = src[(ptrdiff_t)y * sr + x]; }
+        hi = last;
+        HM_SYNC();
+      }
+      const int sb = (y0 - t) % nr;
+      HM_LV(int32_t, vCost);
+      HM_WAVE_FOR(k) {
+        const int ry = k / nx, cx = k - ry * nx, x = x0 + cx, y = y0 + ry;
+        int32_t c = 0x7fffffff;
+        if (ry < np) {
+          uint32_t sum = 0;
+          const Pel *o = org;
+          if (staged) {
+            int s = sb + ry; if (s >= nr) s -= nr;
+            for (int j = 0; j < rows; j++, o += so2) {
+              const Pel *p = win + s * sw + cx;
+#pragma unroll 4
+              for (int i = 0; i < w; i++) sum += (uint32_t)hm_abs(o[i] - p[i]);
+              s += step; if (s >= nr) s -= nr;
+            }
+          } else {
+            const Pel *p = ref + (ptrdiff_t)y * sr + x;
+            for (int j = 0; j < rows; j++, o += so2, p += sr2) {
+#pragma unroll 4
+              for (int i = 0; i < w; i++) sum += (uint32_t)hm_abs(o[i] - p[i]);
+            }
+          }
+          c = (int32_t)(((sum << sub) >> (bd - 8)) + mc_cost32(e, mc_bits(e, x, y)));
+        }
+        HM_LVK(vCost, k) = c;
+      }
+      int pc, lane;
+#ifdef HM355_HOSTSIM
+      pc = 0x7fffffff; lane = 0;
+      for (int k = 0; k < 64; k++) if (vCost[k] < pc) { pc = vCost[k]; lane = k; }
+#else
+      pc = 0x7fffffff - hm_wave_max_i(0x7fffffff - vCost);
+      lane = (int)__builtin_ctzll(__ballot(vCost == pc));
+#endif
+      const int wy = y0 + lane / nx, wx = x0 + lane % nx;
+      if ((uint32_t)pc < best || ((uint32_t)pc == best && (wy < bestY || (wy == bestY && wx < bestX)))) { best = (uint32_t)pc; bestX = wx; bestY = wy; }
+      HM_SYNC();                                        // the pass's reads of the ring end before the next refill
+    }
+  }
+  z->bestSad = best; z->bestX = bestX; z->bestY = bestY; z->bestDist = 0; z->bestRound = 0; z->pointNr = 0;
+  HM_SYNC();
 }
 // xMotionEstimation :3816-3906; results in e->outMv / e->outBits / e->outDist(cost).
 // bi != 0: (inX, inY) is this list's uni-directional MV (search centre, quarter samples) and the pattern is
@@ -734,13 +821,19 @@ HM_DEV HM_NOINLINE void motion_estimation(Shared *e, int cuZ, int cuDepth, int p
   z.subShift = r.h > 8 ? 1 : 0;
   MvD lt, rb, centre = mvPred;
   if (bi) { centre.x = (int16_t)inX; centre.y = (int16_t)inY; }
-  set_search_range(e, centre, bi ? 4 : 64, cuX, cuY, &lt, &rb);   // BipredSearchRange 4 / SearchRange 64
+  const int biRange = me_bipred_range(e);
+  set_search_range(e, centre, bi ? biRange : me_search_range(e), cuX, cuY, &lt, &rb);   // BipredSearchRange / SearchRange
   e->mcost = e->fb.lambdaMotionSAD; e->mvPredictor = mvPred; e->costScale = 2;
   MvD mv = mvPred;
   uint32_t c;
   HM_PROF_BEGIN(e, PR_ME_INT);
-  if (bi) c = pattern_search(e, &z, &mv, lt, rb);
-  else {
+  if (bi) c = pattern_search(e, &z, &mv, lt, rb, biRange);
+  else if (HM_UNI(e->P->fullSearch)) {       // FastSearch=0: m_integerMv2Nx2N is neither read nor written (:3872-3890)
+    z.l = lt.x; z.r = rb.x; z.t = lt.y; z.b = rb.y;
+    full_search(e);
+    mv.x = (int16_t)z.bestX; mv.y = (int16_t)z.bestY;
+    c = z.bestSad - mc_cost32(e, mc_bits(e, z.bestX, z.bestY));
+  } else {
     const int useInt = (partSize != SIZE_2Nx2N || cuDepth != 0);
     MvD im = e->ws->intMv[list][refIdx];
     c = tz_search(e, &z, &mv, cuX, cuY, lt, rb, useInt, im);

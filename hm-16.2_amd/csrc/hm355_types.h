@@ -163,6 +163,10 @@ struct Params {
   Pel *teamWin;                      // team launches: the helpers' private reconstruction windows, HM_TEAM_HELPERS per team (hm355_team.h)
   uint64_t teamWinStride;            // samples per helper window
   int32_t esd, cfm, ecu;             // hm355_set_fast_decisions: early skip detection, CBF fast mode, early CU of P / B slices (TEncCu.cpp:630-657, :644-798, :867)
+  // hm355_set_motion_search: the integer motion search of P / B slices (TEncSearch.cpp:215-217, :3829-3831, :3872).  A zero stands for the
+  // reference's default, so that a Params that was only zero-filled searches as every launch did before the call existed.
+  int32_t fullSearch;                // FastSearch=0: xPatternSearch for uni-prediction too (0: TZ, FastSearch=1)
+  int32_t searchRange, bipredRange;  // SearchRange 1..256 (0: 64), BipredSearchRange 1..16 (0: 4)
 };
 
 struct WorkItem { int32_t frame, ctuX, ctuY, pad; };

@@ -117,7 +117,7 @@ EXPORTS = ["hm355_build_id", "hm355_picture_stats_run", "hm355_picture_stats", "
            "hm355_compress_slice_inter", "hm355_compress_slices_inter", "hm355_deblock", "hm355_deblock_run", "hm355_ref_from_slot", "hm355_ref_release", "hm355_ref_bytes", "hm355_ref_export", "hm355_ref_import", "hm355_sao_run",
            "hm355_num_substreams", "hm355_encode_slices_run", "hm355_encode_slice",
            "hm355_upload_file_frames", "hm355_download_file_frames", "hm355_download_org",
-           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_last_launch_shape", "hm355_dist_batch",
+           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_set_motion_search", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_last_launch_shape", "hm355_dist_batch",
            "hm355_transform_batch"]
 
 
@@ -143,6 +143,7 @@ def load_library(path=LIB_PATH):
     lib.hm355_run_wait.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
     lib.hm355_set_lane_share.argtypes = [C.c_void_p, C.c_int]
     lib.hm355_set_fast_decisions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.hm355_set_motion_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.hm355_set_dqp.argtypes = [C.c_void_p, C.c_int, C.POINTER(DqpDesc)]
     lib.hm355_get_dqp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
     lib.hm355_preanalyze.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -428,6 +429,11 @@ class Encoder:
     def set_fast_decisions(self, esd=0, cfm=0, ecu=0):
         """the reference's --ESD / --CFM / --ECU (each 0 or 1) for every later P / B search of this encoder; sticky until set again"""
         self._check(self.lib.hm355_set_fast_decisions(self.h_, int(esd), int(cfm), int(ecu)), "hm355_set_fast_decisions")
+
+    def set_motion_search(self, fast_search=1, search_range=64, bipred_search_range=4):
+        """the reference's --FastSearch (0 full search, 1 TZ) / --SearchRange (1..256) / --BipredSearchRange (1..16) for every later P / B search of
+        this encoder; sticky until set again"""
+        self._check(self.lib.hm355_set_motion_search(self.h_, int(fast_search), int(search_range), int(bipred_search_range)), "hm355_set_motion_search")
 
     def run_wait(self, lane):
         """wait for the launch of `lane`; returns its kernel time in ms (hm355_run_wait)"""

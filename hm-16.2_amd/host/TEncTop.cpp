@@ -34,6 +34,13 @@ Void TEncTop::create()
     hm355_destroy(m_ctx);
     exit(EXIT_FAILURE);
   }
+  // the integer motion search (TEncSearch::init, TEncSearch.cpp:215-217).  ASR (m_aaiAdaptSR per reference picture) is not reproduced by the library
+  if (getUseASR()) { fprintf(stderr, "TEncTop::create: ASR (adaptive search range) is not supported\n"); hm355_destroy(m_ctx); exit(EXIT_FAILURE); }
+  if (hm355_set_motion_search(m_ctx, getFastSearch(), getSearchRange(), getBipredSearchRange()) != HM355_OK) {
+    fprintf(stderr, "TEncTop::create: %s\n", hm355_last_error(m_ctx));
+    hm355_destroy(m_ctx);
+    exit(EXIT_FAILURE);
+  }
 }
 Void TEncTop::destroy() { for (auto p : m_cListPic) { if (p->getDeviceRef()) hm355_ref_release(m_ctx, p->getDeviceRef()); delete p; } m_cListPic.clear(); if (m_ctx) hm355_destroy(m_ctx); m_ctx = nullptr; }
 Void TEncTop::init() { m_cGOPEncoder.init(this); m_cSliceEncoder.init(this); m_cLoopFilter.init(this); m_cEncSAO.init(this); }

@@ -126,6 +126,12 @@ public:
   Void setUseEarlySkipDetection(Bool b) { m_useEarlySkipDetection = b; } Bool getUseEarlySkipDetection() const { return m_useEarlySkipDetection; }
   Void setUseCbfFastMode(Bool b) { m_bUseCbfFastMode = b; } Bool getUseCbfFastMode() const { return m_bUseCbfFastMode; }
   Void setUseEarlyCU(Bool b) { m_bUseEarlyCU = b; } Bool getUseEarlyCU() const { return m_bUseEarlyCU; }
+  // --FastSearch, --SearchRange, --BipredSearchRange, --ASR (TAppEncCfg.cpp:760-764): the integer motion search; TEncTop::create hands them to hm355_set_motion_search
+  // and stops when ASR is on
+  Void setFastSearch(Int i) { m_iFastSearch = i; } Int getFastSearch() const { return m_iFastSearch; }
+  Void setSearchRange(Int i) { m_iSearchRange = i; } Int getSearchRange() const { return m_iSearchRange; }
+  Void setBipredSearchRange(Int i) { m_bipredSearchRange = i; } Int getBipredSearchRange() const { return m_bipredSearchRange; }
+  Void setUseASR(Bool b) { m_bUseASR = b; } Bool getUseASR() const { return m_bUseASR; }
   Int getPad(Int i) const { return m_aiPad[i]; }     // TEncCfg::m_aiPad: the driver feeds pictures of the coded size, so both are 0
   Int getSourceWidth() const { return m_iSourceWidth; } Int getSourceHeight() const { return m_iSourceHeight; }
   Int getQP() const { return m_iQP; } Int getGOPSize() const { return m_iGOPSize; } Int getIntraPeriod() const { return m_uiIntraPeriod; }
@@ -136,6 +142,7 @@ protected:
   Bool m_bUseAdaptiveQP = false; Int m_iQPAdaptationRange = 6;
   Int m_decodedPictureHashSEIEnabled = 0, m_aiPad[2] = { 0, 0 };
   Bool m_useEarlySkipDetection = false, m_bUseCbfFastMode = false, m_bUseEarlyCU = false;
+  Int m_iFastSearch = 1, m_iSearchRange = 64, m_bipredSearchRange = 4; Bool m_bUseASR = false;
   GOPEntry m_GOPList[16]; Bool m_bUseHADME = true; UInt m_maxNumMergeCand = 5; Int m_TMVPModeId = 1;
 };
 

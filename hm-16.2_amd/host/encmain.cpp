@@ -5,12 +5,14 @@
 //   ... <dump.bin> ldp | ldb | ra [aq[range]] : (aq: --AdaptiveQP=1) the GOP table of cfg/encoder_lowdelay_P_main.cfg / encoder_lowdelay_main.cfg / encoder_randomaccess_main10.cfg (IntraPeriod -1, GOPSize 4, P slices with up to 4 references, loop filters
 //   on); the dump is then a "HMD3" stream in coding order: per picture i32 poc, sliceType, qp, depth, cabacInitType, numRefIdx0, numRefIdx1, colFromL0, mvdL1Zero, refPoc[2][16]; f64 lambda;
 //   u32 numCtus; per CTU the record of tests/hmd2.py CTU_DT (cost, bits, dist, decision arrays, motion arrays, coefficients); the finished planes.
-//   ... hash=N as the last argument (N = 1 MD5, 2 CRC, 3 checksum: --SEIDecodedPictureHash) writes <dump.bin>.picstat: per picture in coding order one line with the
+//   ... hash=N as a trailing argument (N = 1 MD5, 2 CRC, 3 checksum: --SEIDecodedPictureHash) writes <dump.bin>.picstat: per picture in coding order one line with the
 //   two pieces of the reference's log line that depend on the picture, " [Y %6.4lf dB    U %6.4lf dB    V %6.4lf dB]" and " [MD5:...]" / " [CRC:...]" /
 //   " [Checksum:...]" (TEncGOP.cpp:2350, :1789-1802); the dump and the .bits file are what they are without it.
-//   ... fast=<esd><cfm><ecu> as a trailing argument (three digits 0 / 1, in front of hash=N when both are given): --ESD / --CFM / --ECU, the fast encoder
+//   ... fast=<esd><cfm><ecu> as a trailing argument (three digits 0 / 1): --ESD / --CFM / --ECU, the fast encoder
 //   decisions of P / B slices (TEncCfg::setUseEarlySkipDetection, setUseCbfFastMode, setUseEarlyCU -> hm355_set_fast_decisions).  Without the argument the
 //   environment variable HM355_FAST=<esd><cfm><ecu> is read the same way (for callers that build the command line themselves, such as bench.py --workload c3).
+//   ... me=<fast>,<range>,<bipred> as a trailing argument: --FastSearch / --SearchRange / --BipredSearchRange, the integer motion search of P / B slices
+//   (TEncCfg::setFastSearch, setSearchRange, setBipredSearchRange -> hm355_set_motion_search).  The trailing fast=, me= and hash= arguments come in any order.
 // The slice data of every picture (TEncSlice::encodeSlice) goes to <dump.bin>.bits: per picture u32 numSubstreams, then per substream u32 size + bytes.
 #include "TEncTop.h"
 #include <stdio.h>
@@ -52,7 +54,8 @@ int main(int argc, char **argv)
       enc.setGOPEntry(i, e);
     }
   }
-  const int hashMethod = argc > 9 && !strncmp(argv[argc - 1], "hash=", 5) ? atoi(argv[argc - 1] + 5) : 0;
+  int hashMethod = 0;
+  for (int i = 9; i < argc; i++) if (!strncmp(argv[i], "hash=", 5)) hashMethod = atoi(argv[i] + 5);
   enc.setDecodedPictureHashSEIEnabled(hashMethod);
   const char *fast = getenv("HM355_FAST");
   if (fast) fprintf(stderr, "hm355_encmain: HM355_FAST=%s from the environment sets the fast decisions (a fast= argument overrides it)\n", fast);
@@ -60,6 +63,11 @@ int main(int argc, char **argv)
   if (fast) {
     if (strlen(fast) != 3 || strspn(fast, "01") != 3) { fprintf(stderr, "fast=<esd><cfm><ecu>: three digits 0 / 1\n"); return 2; }
     enc.setUseEarlySkipDetection(fast[0] == '1'); enc.setUseCbfFastMode(fast[1] == '1'); enc.setUseEarlyCU(fast[2] == '1');
+  }
+  for (int i = 9; i < argc; i++) if (!strncmp(argv[i], "me=", 3)) {
+    int fs, sr, bi; char end;
+    if (sscanf(argv[i] + 3, "%d,%d,%d%c", &fs, &sr, &bi, &end) != 3) { fprintf(stderr, "me=<fast>,<range>,<bipred>: three integers\n"); return 2; }
+    enc.setFastSearch(fs); enc.setSearchRange(sr); enc.setBipredSearchRange(bi);
   }
   enc.create(); enc.init();
   FILE *fs = hashMethod ? fopen((std::string(argv[8]) + ".picstat").c_str(), "w") : NULL;

@@ -303,6 +303,14 @@ int hm355_run_wait(hm355_ctx *ctx, int lane, double *kernel_ms);
  * (hm355_compress_slice(s)_inter, hm355_slice_begin_inter + hm355_run_ctus); I slices ignore it, whichever entry point searches them.  With any switch on, a P / B launch is searched by one wavefront per CTU (no wavefront teams, whatever HM355_TEAM says).
  * HM355_ERR_ARG: a value other than 0 or 1; a slice open on any slot; a hm355_run_begin launch outstanding. */
 int hm355_set_fast_decisions(hm355_ctx *ctx, int esd, int cfm, int ecu);
+/* The reference's integer motion search of P / B slices (TEncSearch.cpp:215-217, :3829-3831, :3872): --FastSearch (1: TZ, 0: the exhaustive
+ * xPatternSearch for uni-prediction too), --SearchRange 1..256 and --BipredSearchRange 1..16; defaults 1 / 64 / 4.  Sticky, per context, and
+ * followed by every later search of a P / B slice like hm355_set_fast_decisions; I slices ignore it.  With fast_search 0 a P / B launch is
+ * searched by one wavefront per CTU (no wavefront teams, whatever HM355_TEAM says).  Not built and rejected: FastSearch=2 (the selective TZ
+ * search, :4016); ASR, the adaptive search range, has no parameter here -- a caller whose configuration turns it on must not bind.
+ * HM355_ERR_ARG with a message in hm355_last_error: any other value; a slice open on any slot; a hm355_run_begin launch outstanding.  A
+ * rejected call leaves the previous setting in force. */
+int hm355_set_motion_search(hm355_ctx *ctx, int fast_search, int search_range, int bipred_search_range);
 
 /* CTU-row bands (TEncSlice.cpp:740-755,855-858 are the WPP hand-off points a band boundary cuts through): a picture is
  * searched by several devices, each owning a band of whole CTU rows [first_row, last_row] of the pictures in slots
