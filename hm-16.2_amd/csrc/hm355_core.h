@@ -330,6 +330,8 @@ struct RefLds {
 // slot index: CI_CURR_BEST / CI_NEXT_BEST are never addressed at depth 4
 #define HM_SLOT(d, ci) ((d) * CI_NUM + (ci) - ((d) == 4 ? 2 : 0))
 #define HM_NUM_SLOTS (4 * CI_NUM + 3)
+#define HM_SLOT_CU_LUMA HM_NUM_SLOTS           // est_intra_pred_qt: the estimator after the count of the CU's final luma tree (2Nx2N, I slice)
+#define HM_SLOT_CU_CHROMA (HM_NUM_SLOTS + 1)   // est_intra_pred_chroma_qt: the estimator after the count of the winning chroma mode
 struct Team;                           // hm355_team.h: the wavefronts of one workgroup searching one CTU together (latency mode)
 #if defined(HM355_PROFILE) && !defined(HM355_HOSTSIM)
 #define HM_CTU_WAVES 11                 /* diagnostic build: the cycle counters of the searches take the LDS of the twelfth */
@@ -2291,6 +2293,10 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_qt(Shared *e, int cuZ, int cuDepth)
         HM_PAR_FOR(i, puParts) { ws->tmpTr[i] = m->tr[z + i]; for (int c = 0; c < 3; c++) { ws->tmpCbf[c][i] = m->cbf[c][z + i]; ws->tmpTs[c][i] = m->ts[c][z + i]; } }
         HM_SYNC();
         if (!last && n == 32) cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_QT_TRAFO_TEST)], &e->cur);
+        // Every way recur_intra_coding_qt closes the root leaves e->cur after ONE count of the tree it kept, taken from the CU's snapshot with the
+        // bit counter reset: the unsplit TU's count (intra_bits_qt, the winner's lane, or the parked first-pass state), or the recount of the
+        // split root.  Parked for cu_bits_from_passes; the last improvement is the PU's result.
+        if (!nxn && !e->im) cabac_copy(&e->ws->slot[HM_SLOT_CU_LUMA], &e->cur);
       }
     }
     overallDistY += bestPUDistY;
@@ -2393,8 +2399,15 @@ HM_DEV inline void set_intra_result_chroma_qt(Shared *e, const TU *root)
     return 0;
   });
 }
+#if defined(HM355_CHECK_CU_BITS)
+static int g_cub_chroma_path;            // which way the CU's chroma went, for cu_bits_check's report: 0 wave-uniform loop, 1 simt4_chroma_cu, 2 simt8_chroma_cu16
+#define HM_CUB_CHROMA_PATH(v) (g_cub_chroma_path = (v))
+#else
+#define HM_CUB_CHROMA_PATH(v) ((void)0)
+#endif
 HM_DEV HM_NOINLINE uint32_t est_intra_pred_chroma_qt(Shared *e, int cuZ, int cuDepth)
 {
+  HM_CUB_CHROMA_PATH(0);
   HM_ENTRY(e); cuZ = HM_UNI(cuZ); cuDepth = HM_UNI(cuDepth);
   CtuMeta *m = (&e->meta); WorkSpace *ws = e->ws; const int cuParts = 256 >> (2 * cuDepth);
   const TU t = tu_root(e, cuZ, cuDepth);
@@ -2407,8 +2420,10 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_chroma_qt(Shared *e, int cuZ, int cuD
     if (!tsLuma) {
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
       HM_PROF_BEGIN(e, PR_S4C);
+      HM_CUB_CHROMA_PATH(1);
       const uint32_t d = HM_UCALL(simt4_chroma_cu(e, split ? tu_child(&t, 0, 0) : t, cuZ));
       HM_PROF_END(e, PR_S4C);
+      cabac_copy(&e->ws->slot[HM_SLOT_CU_CHROMA], &e->cur);            // the winning mode's lane, for cu_bits_from_passes
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
       return d;
     }
@@ -2420,8 +2435,10 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_chroma_qt(Shared *e, int cuZ, int cuD
     if (!split) {
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
       HM_PROF_BEGIN(e, PR_S8C);
+      HM_CUB_CHROMA_PATH(2);
       const uint32_t d = HM_UCALL(simt8_chroma_cu16(e, cuZ));
       HM_PROF_END(e, PR_S8C);
+      cabac_copy(&e->ws->slot[HM_SLOT_CU_CHROMA], &e->cur);
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
       return d;
     }
@@ -2438,6 +2455,7 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_chroma_qt(Shared *e, int cuZ, int cuD
     const double cost = calc_rd_cost(e, bits, dist);
     if (cost < bestCost) {
       bestCost = cost; bestDist = dist; bestMode = modeList[mi];
+      cabac_copy(&e->ws->slot[HM_SLOT_CU_CHROMA], &e->cur);            // the estimator after this mode's count (from the CU's snapshot, bit counter reset), for cu_bits_from_passes
       set_intra_result_chroma_qt(e, &t);
       HM_PAR_FOR(i, cuParts) for (int c = 1; c < 3; c++) { ws->saveCbf[c][i] = m->cbf[c][cuZ + i]; ws->saveTs[c][i] = m->ts[c][cuZ + i]; }
       HM_SYNC();
@@ -2601,6 +2619,109 @@ HM_DEV HM_NOINLINE void restore_best_from(Shared *e, const Best *b, int cuZ, int
 }
 HM_DEV inline void restore_best(Shared *e, int cuZ, int cuDepth) { restore_best_from(e, &e->ws->best[cuDepth], cuZ, cuDepth); }
 
+// ------------------------------------------------------------------------------------------------
+// The bit count and the estimator state of an intra CU from the counts its search already made, instead of coding the CU's syntax once more
+// (the close of xCheckRDCostIntra, TEncCu.cpp:1601-1626).  The estimator's count is a running sum of Q15 prices, the bit counter reset keeps its
+// low 15 bits, a bin's price depends only on the state of its own context and a bypass bin costs 32768 anywhere.  For a 2Nx2N CU of an I slice the
+// bins of the CU syntax are those of two counts of the search, both taken from the CU's snapshot with the bit counter reset:
+//   luma    est_intra_pred_qt closes with one count of the final luma tree (part size, luma mode, transform splits, luma cbfs, luma coefficients)
+//   chroma  est_intra_pred_chroma_qt counts every chroma mode (chroma mode, cbf_cb / cbf_cr, chroma coefficients); the winner's is kept
+// and the two touch disjoint contexts (HM_CHROMA_CTX_TABLE, hm355_types.h).  So with f0 the fraction the snapshot carries and L, C what the two
+// counts added, the CU syntax adds L + C to f0, and leaves the luma count's contexts with the chroma table's ranges taken from the chroma count --
+// provided every context sees its bins in the same order.  The CU syntax goes transform unit by transform unit (Y, Cb, Cr) where the counts go
+// component by component; Cb and Cr share their contexts, so a CU with several chroma blocks per component, coefficients in both, codes them in
+// another order (Cb0 Cr0 Cb1 Cr1 ... against Cb0 Cb1 ... Cr0 Cr1 ...).  Those CUs count their chroma syntax again, in the CU syntax's order, on top
+// of the luma count (CUB_CHROMA_RECOUNT); cu_bits_class names the CUs that keep the whole recount.
+// ------------------------------------------------------------------------------------------------
+enum { CUB_RECOUNT = 0, CUB_MERGE, CUB_CHROMA_RECOUNT };
+HM_DEV inline int cu_bits_class(const Shared *e, int cuZ, int cuDepth, int partSize)
+{
+  if (partSize != SIZE_2Nx2N || e->im || e->fb.dqp) return CUB_RECOUNT;           // the table in hm355_types.h
+  const CtuMeta *m = (&e->meta);
+  // more than one chroma block per component: a split transform tree above the 8x8 CU (whose four luma blocks share one chroma block per component)
+  if (cuDepth < 3 && m->tr[cuZ] != 0 && (m->cbf[1][cuZ] & 1) && (m->cbf[2][cuZ] & 1)) return CUB_CHROMA_RECOUNT;
+  return CUB_MERGE;
+}
+HM_DEV inline int hm_is_chroma_ctx(int i)
+{
+#define HM_CHROMA_CTX_IN(a, b) || (i >= (a) && i < (b))
+  return 0 HM_CHROMA_CTX_TABLE(HM_CHROMA_CTX_IN);
+#undef HM_CHROMA_CTX_IN
+}
+// the chroma part of encode_cu_syntax on the estimator itself: chroma mode, then cbf_cb / cbf_cr and the chroma coefficients in the transform tree's order
+HM_DEV HM_NOINLINE void encode_cu_chroma_syntax(Shared *e, int cuZ, int cuDepth)
+{
+  HM_ENTRY(e); cuZ = HM_UNI(cuZ); cuDepth = HM_UNI(cuDepth);
+  const CtuMeta *m = (&e->meta); Cabac *c = &e->cur;
+  code_intra_dir_chroma(e, c, cuZ);
+  const TU root = tu_root(e, cuZ, cuDepth);
+  tu_walk(e->walkOuter, &root, 1, [&](const TU *t) {
+    const int subdiv = m->tr[t->cuZ + t->relZ] > t->trDepth;
+    code_chroma_cbfs(e, c, t, subdiv);
+    if (subdiv) return 1;
+    for (int comp = 1; comp < 3; comp++) code_tu_coeff(e, c, t, comp, e->cc, 1);
+    return 0;
+  });
+}
+// e->cur holds the CU's snapshot (both passes return to it); the two counts are parked in the workspace
+HM_DEV inline void cu_bits_from_passes(Shared *e, int cuZ, int cuDepth, int how)
+{
+  const Cabac *L = &e->ws->slot[HM_SLOT_CU_LUMA], *C = &e->ws->slot[HM_SLOT_CU_CHROMA];
+  if (how == CUB_CHROMA_RECOUNT) {       // f0 + L is the luma count's own fraction, and the chroma contexts are still the snapshot's there
+    cabac_copy(&e->cur, L);
+    encode_cu_chroma_syntax(e, cuZ, cuDepth);
+    return;
+  }
+  const uint64_t *lp = (const uint64_t *)L, *cp = (const uint64_t *)C; uint64_t *dp = (uint64_t *)&e->cur;
+  HM_PAR_FOR(i, (int)(sizeof(Cabac) / 8)) {        // word by word as cabac_copy parked them
+    if (i == (int)(offsetof(Cabac, frac) / 8)) dp[i] = lp[i] + cp[i] - (dp[i] & 32767);          // (f0 + L) + (f0 + C) - f0
+    else {
+      uint64_t mask = 0;
+      for (int b = 0; b < 8; b++) if (hm_is_chroma_ctx(8 * i + b)) mask |= 0xffull << (8 * b);
+      dp[i] = (lp[i] & ~mask) | (cp[i] & mask);
+    }
+  }
+  HM_SYNC();
+}
+#if defined(HM355_CHECK_CU_BITS)
+// Diagnostic build of the host twin only (never the product): both ways for every CU that does not recount; a difference in the count or in any context
+// is reported and the run fails.  A summary line with the number of 2Nx2N I-slice CU evaluations of each class goes to stderr when the program ends.
+#ifndef HM355_HOSTSIM
+#error "HM355_CHECK_CU_BITS is a diagnostic of the host twin"
+#endif
+#include <stdio.h>
+#include <stdlib.h>
+#include <unistd.h>
+static unsigned long long g_cub_n[3], g_cub_bad;
+static void cu_bits_report(void)
+{
+  fprintf(stderr, "CU_BITS merged %llu chroma_recount %llu recount %llu mismatch %llu\n", g_cub_n[CUB_MERGE], g_cub_n[CUB_CHROMA_RECOUNT], g_cub_n[CUB_RECOUNT], g_cub_bad);
+  fflush(stderr);
+  if (g_cub_bad) _exit(3);
+}
+static inline void cu_bits_check(Shared *e, int cuZ, int cuDepth, int partSize, int how)
+{
+  static int registered = 0;
+  if (!registered) { registered = 1; atexit(cu_bits_report); }
+  if (partSize != SIZE_2Nx2N || e->im) return;
+  g_cub_n[how]++;
+  if (how == CUB_RECOUNT) return;
+  const Cabac got = e->cur;
+  cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
+  reset_bits(&e->cur);
+  encode_cu_syntax(e, &e->cur, cuZ, cuDepth);        // the search goes on from the recount's state: every report stands for its own CU
+  int firstBad = -1;
+  for (int i = HM_NUM_CTX - 1; i >= 0; i--) if (got.s[i] != e->cur.s[i]) firstBad = i;
+  if (firstBad < 0 && got.frac == e->cur.frac) return;
+  g_cub_bad++;
+  const CtuMeta *m = (&e->meta);
+  static const char *const chromaPath[3] = { "wave-uniform", "simt4_chroma_cu", "simt8_chroma_cu16" };
+  const char *closing = m->tr[cuZ] ? "split root" : (cuDepth >= 2 ? "winner's lane (s8Reuse 1)" : "parked first pass (s8Reuse 2)");
+  fprintf(stderr, "CU_BITS mismatch: frame CTU %d cuZ %d depth %d class %d, luma closing: %s, chroma: %s; frac %llu, recount %llu; first context that differs %d\n",
+          e->ctuAddr, cuZ, cuDepth, how, closing, chromaPath[g_cub_chroma_path], (unsigned long long)got.frac, (unsigned long long)e->cur.frac, firstBad);
+}
+#endif
+
 // xCheckRDCostIntra, TEncCu.cpp:1574-1646; leaves the trial in place
 HM_DEV HM_NOINLINE void check_rd_cost_intra(Shared *e, int cuZ, int cuDepth, int partSize)
 {
@@ -2620,8 +2741,14 @@ HM_DEV HM_NOINLINE void check_rd_cost_intra(Shared *e, int cuZ, int cuDepth, int
     par_copy_blk(e->fb.rec[0] + (e->ctuY * 64 + y) * ps + e->ctuX * 64 + x, ps, e->ws->reco + y * 64 + x, 64, n);
   }
   { HM_PROF_BEGIN(e, PR_CHROMA); d += HM_UCALL(est_intra_pred_chroma_qt(e, cuZ, cuDepth)); HM_PROF_END(e, PR_CHROMA); }
-  reset_bits(&e->cur);
-  { HM_PROF_BEGIN(e, PR_ENCCU); encode_cu_syntax(e, &e->cur, cuZ, cuDepth); HM_PROF_END(e, PR_ENCCU); }
+  HM_PROF_BEGIN(e, PR_ENCCU);
+  const int how = cu_bits_class(e, cuZ, cuDepth, partSize);
+  if (how == CUB_RECOUNT) { reset_bits(&e->cur); encode_cu_syntax(e, &e->cur, cuZ, cuDepth); }
+  else cu_bits_from_passes(e, cuZ, cuDepth, how);
+  HM_PROF_END(e, PR_ENCCU);
+#if defined(HM355_CHECK_CU_BITS)
+  cu_bits_check(e, cuZ, cuDepth, partSize, how);
+#endif
   cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)], &e->cur);
   e->outBits = num_bits(&e->cur); e->outDist = d;
   e->outCost = calc_rd_cost(e, e->outBits, e->outDist);

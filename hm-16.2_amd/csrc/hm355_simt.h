@@ -120,6 +120,17 @@ template <int L2> HM_FINL void simt_store_contexts(const Simt<L2> &S, int k, Cab
 {
   HM_PAR_FOR(j, SimtDim<L2>::NCTX) cb->s[simt_ctx_index<L2>(j, 0, cbfCodeCtx, C_INTRA_LUMA)] = S.ctx(j, k);
 }
+// the estimator after job k of a chroma-mode batch (simt4_chroma_cu, simt8_chroma_cu16: cbf at the CU's root TU, the chroma prediction mode): the
+// contexts the lane advanced and its Q15 count.  The copies a chroma block has no context for (simt_setup's `none`) alias others and are left out.
+template <int L2> HM_FINL void simt_store_chroma_mode(const Simt<L2> &S, int k, Cabac *cb, uint32_t frac)
+{
+  typedef SimtDim<L2> D;
+  HM_PAR_FOR(j, D::NCTX) {
+    const int none = (j < D::X_ONE && j >= 16) || (j >= D::X_ONE && j < D::X_ABS && j - D::X_ONE >= 8) || (j >= D::X_ABS && j < D::X_LX && j - D::X_ABS >= 2);
+    if (!none) cb->s[simt_ctx_index<L2>(j, 1, 5, C_CHROMA_PRED)] = S.ctx(j, k);
+  }
+  cb->frac = (uint64_t)frac;
+}
 
 // one context-coded bin on job k's private context copy; frac counts Q15 bits
 template <int L2> HM_DEV inline void simt_bin(const Shared *e, const Simt<L2> &S, int k, uint32_t *frac, int c, int bin)

@@ -317,7 +317,7 @@ HM_DEV HM_NOINLINE uint32_t simt4_chroma_cu(Shared *e, TU leafv, int cuZ)
       if (cbfU) s4_code_coeff(e, S, k, k, 1, scanType, 0, &frac);
       if (cbfV) s4_code_coeff(e, S, k, k + 1, 1, scanType, 0, &frac);
       const uint32_t bits = frac >> 15, dist = A->outDist[k] + A->outDist[k + 1];
-      A->outBits[k] = dist;
+      A->outBits[k] = dist; A->outBits[k + 1] = frac;                // the odd entries are free: the mode's Q15 count
       A->outCost[k] = calc_rd_cost(e, bits, dist);
     }
   }
@@ -339,6 +339,7 @@ HM_DEV HM_NOINLINE uint32_t simt4_chroma_cu(Shared *e, TU leafv, int cuZ)
     const int vU = t->trDepth ? 3 * cbfU : cbfU, vV = t->trDepth ? 3 * cbfV : cbfV, bm = chroma_mode_at(modeList, best);
     HM_PAR_FOR(i, 4) { m->cbf[1][cuZ + i] = (uint8_t)vU; m->cbf[2][cuZ + i] = (uint8_t)vV; m->ts[1][cuZ + i] = 0; m->ts[2][cuZ + i] = 0; m->dirC[cuZ + i] = (uint8_t)bm; }
   }
+  simt_store_chroma_mode(S, 2 * best, &e->cur, A->outBits[2 * best + 1]);      // e->cur: the estimator after the winning mode's count
   HM_SYNC();
   return bestDist;
 }

@@ -231,6 +231,7 @@ HM_DEV HM_NOINLINE uint32_t simt8_chroma_cu16(Shared *e, int cuZ)
           if (cbfU) simt_code_coeff(e, S, k, k, 1, SCAN_DIAG, &frac);
           if (cbfV) simt_code_coeff(e, S, k, k + 1, 1, SCAN_DIAG, &frac);
           const uint32_t dist = A->outDist[k] + A->outDist[k + 1];
+          A->outFrac[k] = frac;
           A->outCost[k] = calc_rd_cost(e, frac >> 15, dist);
         }
       }
@@ -262,6 +263,7 @@ HM_DEV HM_NOINLINE uint32_t simt8_chroma_cu16(Shared *e, int cuZ)
   const uint32_t bestDist = A->outDist[2 * best] + A->outDist[2 * best + 1];
   const int bm = modeList[best];
   HM_PAR_FOR(i, 16) { m->cbf[1][cuZ + i] = (uint8_t)cbfU; m->cbf[2][cuZ + i] = (uint8_t)cbfV; m->ts[1][cuZ + i] = 0; m->ts[2][cuZ + i] = 0; m->dirC[cuZ + i] = (uint8_t)bm; }
+  simt_store_chroma_mode(S, 2 * best, &e->cur, A->outFrac[2 * best]);          // e->cur: the estimator after the winning mode's count
   HM_SYNC();
   return bestDist;
 }

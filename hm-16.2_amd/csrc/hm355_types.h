@@ -19,6 +19,27 @@ struct Cabac {
   uint8_t s[184];          // HM_NUM_CTX used, padded to 8-byte multiple
   uint64_t frac;           // TEncBinCABAC::m_fracBits
 };
+// The contexts only the chroma syntax of an intra CU codes, as [first, end) ranges: its luma syntax (part size, luma mode, transform split, luma
+// cbf, luma coefficients) codes none of them and its chroma syntax codes no other.  A 2Nx2N CU of an I slice therefore takes its bit count and
+// its estimator state from the luma pass and the winning chroma mode's pass of its search (cu_bits_from_passes, hm355_core.h) instead of coding
+// its syntax once more.  The CUs that keep that recount, and why:
+//   NxN CUs                                    the four luma modes are coded together, but each PU was priced from its own snapshot
+//   CUs of P / B slices                        the skip and prediction-mode bins come on top (not built)
+//   any CU while cu_qp_delta is on             the delta-QP bins go into the transform tree (C_DQP)
+// and one class recounts the chroma syntax only, on top of the luma pass's state:
+//   CUs above 8x8 with a split transform tree  Cb and Cr share every context of this table, the pass codes all Cb blocks and then all Cr blocks
+//   and both cbf_cb and cbf_cr set             where the CU syntax goes transform unit by transform unit: with more than one chroma block per
+//                                              component the bins reach the shared contexts in another order
+#define HM_CHROMA_CTX_TABLE(X) \
+  X(C_CHROMA_PRED, C_SUBDIV)         /* intra_chroma_pred_mode */ \
+  X(C_QT_CBF + 5, C_SIG_CG)          /* cbf_cb / cbf_cr, by transform depth */ \
+  X(C_SIG_CG + 2, C_SIG)             /* coded_sub_block_flag */ \
+  X(C_SIG + 28, C_LASTX)             /* sig_coeff_flag */ \
+  X(C_LASTX + 15, C_LASTY)           /* last_sig_coeff_x_prefix */ \
+  X(C_LASTY + 15, C_ONE)             /* last_sig_coeff_y_prefix */ \
+  X(C_ONE + 16, C_ABS)               /* coeff_abs_level_greater1_flag */ \
+  X(C_ABS + 4, C_TSKIP)              /* coeff_abs_level_greater2_flag */ \
+  X(C_TSKIP + 1, C_SKIP)             /* transform_skip_flag */
 enum { CI_CURR_BEST = 0, CI_NEXT_BEST, CI_TEMP_BEST, CI_QT_TRAFO_TEST, CI_QT_TRAFO_ROOT, CI_NUM };   // TypeDef.h:477-486 minus the unused CI_CHROMA_INTRA
 
 // ---- per-CTU decision arrays, 256 4x4 partitions in z-scan order ----
@@ -78,7 +99,8 @@ struct WorkSpace {
   MvD intMv[2][16];                  // TEncSearch::m_integerMv2Nx2N[list][refIdx] of the search in progress (read and written once per motion search)
   Pel tsPred[3][16], tsRec[3][16]; TCoeff tsCoef[3][16];   // the parked first trial of a 4x4 transform-skip decision (wave-uniform path; rare since the candidates-in-lanes paths)
   double costCoeff[1024];            // RDOQ of 32x32 blocks: cost of the positions that keep a non-zero level (everything else of its per-position state is in LDS)
-  Cabac slot[4 * CI_NUM + 3];        // m_pppcRDSbacCoder[depth][CI_*] snapshots (the live coder stays in LDS); depth 4 only holds TEMP_BEST/QT_TRAFO_*
+  Cabac slot[4 * CI_NUM + 3 + 2];    // m_pppcRDSbacCoder[depth][CI_*] snapshots (the live coder stays in LDS); depth 4 only holds TEMP_BEST/QT_TRAFO_*; then the
+                                     // estimator after the luma pass and after the winning chroma mode's pass of the 2Nx2N intra CU under evaluation (HM_SLOT_CU_*)
   Pel tmpPred[HM_COEF_CTU];          // m_tmpYuvPred (merge / ME prediction error)
   Pel resiBest[HM_COEF_CTU];         // m_ppcResiYuvBest[depth]
   Pel mcTmp[72 * 64];                // first interpolation stage of a block (m_filteredBlockTmp)
