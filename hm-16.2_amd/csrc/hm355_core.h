@@ -270,7 +270,8 @@ HM_CONST int32_t HM_QUANT_SCALES[6] = {26214, 23302, 20560, 18396, 16384, 14564}
 HM_CONST int32_t HM_INV_QUANT_SCALES[6] = {40, 45, 51, 57, 64, 72};
 HM_CONST uint8_t HM_GROUP_IDX[32] = {0,1,2,3,4,4,5,5,6,6,6,6,7,7,7,7,8,8,8,8,8,8,8,8,9,9,9,9,9,9,9,9};
 HM_CONST uint8_t HM_CTX_IND_MAP_4x4[16] = {0,1,4,5, 2,3,4,5, 6,6,8,8, 7,7,8,8};
-HM_CONST uint8_t HM_INTRA_MODE_NUM_FAST[6] = {3, 8, 8, 3, 3, 3};
+enum { HM_INTRA_FAST_8x8 = 8, HM_NUM_MPM = 3 };     // RD candidates by SATD of an 8x8 PU; most probable modes a PU can add to them (est_intra_pred_qt)
+HM_CONST uint8_t HM_INTRA_MODE_NUM_FAST[6] = {3, 8, HM_INTRA_FAST_8x8, 3, 3, 3};
 HM_CONST uint8_t HM_INTRA_FILTER[5] = {10, 7, 1, 0, 10};
 HM_CONST int8_t HM_ANG_TABLE[9] = {0, 2, 5, 9, 13, 17, 21, 26, 32};
 HM_CONST int16_t HM_INV_ANG_TABLE[9] = {0, 4096, 1638, 910, 630, 482, 390, 315, 256};
@@ -363,7 +364,7 @@ struct Shared {
   // results handed back by the big non-inlined stages (instead of pointers to private memory)
   double outCost; uint32_t outBits, outDist; double outRdCost;
   int32_t mpmZ;                        // the PU whose most-probable-mode list is tabulated below (-1: none)
-  int32_t s8Winner, s8Reuse;           // 8x8 and 16x16 PUs alike (hm355_simt8.h / hm355_simt16.h): the first pass's winning candidate (slot | place in the list << 8); set while its evaluation can stand in for the closing pass's unsplit TU
+  int32_t s8Winner, s8Reuse;           // 8x8 and 16x16 PUs alike, despite the name (simt_luma_first_pass, hm355_simt.h): the first pass's winning candidate (slot | place in the list << 8); set while its evaluation can stand in for the closing pass's unsplit TU
   // inter (P / B slice) state that outlives a stage
   InterMeta *im;                       // motion arrays of the CTU under search (HBM)
   uint32_t mcost; MvD mvPredictor; int32_t costScale;   // TComRdCost motion-cost state
@@ -2025,7 +2026,7 @@ HM_DEV inline void load_intra_result_qt(Shared *e, const TU *t, int comp)
 // ------------------------------------------------------------------------------------------------
 // returns distortion through *distY and adds the RD cost to *rdCost, exactly like the recursive reference
 HM_DEV HM_NOINLINE void simt4_luma_leaf(Shared *e, TU tv);      // hm355_simt4.h
-template <int L2> HM_DEV HM_NOINLINE void simt_luma_winner_as_single_tu(Shared *e, TU tv);      // hm355_simt16.h
+template <int L2> HM_DEV HM_NOINLINE void simt_luma_winner_as_single_tu(Shared *e, TU tv);      // hm355_simt.h
 HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirst)
 {
   HM_ENTRY(e); checkFirst = HM_UNI(checkFirst); rootv = hm_uni_struct(rootv);
@@ -2205,7 +2206,7 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_qt(Shared *e, int cuZ, int cuDepth)
       init_adi_pattern(e, 0, e->ctuX * 64 + t.x, e->ctuY * 64 + t.y, n, e->ctuX * 16 + (r & 15), e->ctuY * 16 + (r >> 4), n / 4, 1);
       const Pel *org = e->fb.org[0] + (e->ctuY * 64 + t.y) * ps + e->ctuX * 64 + t.x;
       Pel *pred = ws->pred + t.y * 64 + t.x;
-      int preds[3];
+      int preds[HM_NUM_MPM];
       const int numMpm = intra_dir_predictor(e, z, preds);
       e->mpmZ = z; e->mpmNum = numMpm; e->mpmPreds[0] = preds[0]; e->mpmPreds[1] = preds[1]; e->mpmPreds[2] = preds[2];
       // xModeBitsIntra (TEncSearch.cpp:5456-5478) depends only on whether the mode is an MPM and which
@@ -2268,12 +2269,12 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_qt(Shared *e, int cuZ, int cuDepth)
     int firstPass = 0;
     if (n == 8 || n == 16) {
       // 8x8 and 16x16 PUs (2Nx2N CUs of depth 3 and 2): the first pass over the candidates only ranks them -- each is one unsplit transform
-      // block from the same snapshot -- so it runs with the candidates in lanes (hm355_simt8.h, hm355_simt16.h) and only the closing pass with
+      // block from the same snapshot -- so it runs with the candidates in lanes (simt_luma_first_pass, hm355_simt.h) and only the closing pass with
       // the full residual quadtree follows.  That pass starts with the very evaluation the winner had in the first pass, so its result is
       // the first-pass result or better, and is taken as the reference takes it (:2566-2600).
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(cuDepth, CI_CURR_BEST)]);
-      if (n == 8) { HM_PROF_BEGIN(e, PR_S8L); bestPUMode = HM_UCALL(simt8_luma_first_pass(e, t, numModesForFullRD)); HM_PROF_END(e, PR_S8L); }
-      else { HM_PROF_BEGIN(e, PR_S16L); bestPUMode = HM_UCALL(simt16_luma_first_pass(e, t, numModesForFullRD)); HM_PROF_END(e, PR_S16L); }
+      if (n == 8) { HM_PROF_BEGIN(e, PR_S8L); bestPUMode = HM_UCALL(simt_luma_first_pass<3>(e, t, numModesForFullRD)); HM_PROF_END(e, PR_S8L); }
+      else { HM_PROF_BEGIN(e, PR_S16L); bestPUMode = HM_UCALL(simt_luma_first_pass<4>(e, t, numModesForFullRD)); HM_PROF_END(e, PR_S16L); }
       firstPass = numModesForFullRD;
       e->s8Reuse = 1;
     }

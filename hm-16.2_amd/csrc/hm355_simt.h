@@ -11,8 +11,15 @@
 //   put_lev / lev                            final signed level of job k
 //   cg_pos(scanType, cg)                     raster position of coefficient group cg
 //   sig_inc(scanType, firstCtx, pattern, sp, chroma)   significance context increment
-//   KEEPS_COST, keep_cost(), cost_at()       whether RDOQ stores the cost of each decided level (4x4) or prices it again (8x8)
-// Then the small derivations the entry points have in common.  Included from hm355_core.h in front of the two.
+//   KEEPS_COST, keep_cost(), cost_at()       whether RDOQ stores the cost of each decided level (4x4) or prices it again (8x8, 16x16)
+//   out_cbf / out_dist / out_frac / out_cost(k)   results of job k: coded block flag, distortion, Q15 bit count, RD cost
+//   tile(stage), TS                          8x8, 16x16: the two stages of the transform tile under the lanes and its row stride
+//   luma_scan(mode), ONE_BATCH               8x8, 16x16: scan type of a luma mode at this size; whether the longest candidate list fits one batch
+// Then the small derivations the entry points have in common, the pricing of the five chroma modes of a CU (simt_pick_chroma_mode: 4x4 and
+// 8x8 chroma blocks) and what 8x8 and 16x16 blocks share beyond the coder: the three sample passes (simt_residual_fwd, simt_dequant_inv1,
+// simt_inv2_recon), the first pass over the candidates of a luma PU (simt_luma_first_pass) and the hand-over of its winner to the closing
+// pass (simt_luma_winner_as_single_tu).  All are templates on L2, instantiated once the size's Simt<L2> is defined.  Included from
+// hm355_core.h in front of the three.
 #pragma once
 
 // Context numbering inside a batch: X_* index the per-job context copies (Simt<L2>::A->ctx), T_* the bit costs of the batch's
@@ -433,3 +440,255 @@ HM_FINL void allowed_chroma_dirs(int lumaDir, int *list)
 }
 HM_FINL int chroma_mode_at(const int *list, int mi)              // list[mi] for a per-lane mi, with the list staying in registers
 { return mi == 0 ? list[0] : (mi == 1 ? list[1] : (mi == 2 ? list[2] : (mi == 3 ? list[3] : list[4]))); }
+
+// ---- the five chroma modes of a CU, jobs 2 * modeIndex + component - 1 evaluated (out_cbf, out_dist): lane 2 * modeIndex counts the mode's
+// bits on its own context copy -- chroma prediction mode (codeIntraDirChroma :692), both cbfs at the CU's root TU (xEncSubdivCbfQT :856), Cb then
+// Cr coefficients (xGetIntraBitsQT :1038) -- and its cost; then the reference's comparison in list order, strict "<".  code(k, src, &frac): the
+// coefficient bits of job src's block on lane k's contexts (the size's coder with its scan).  Returns the winning mode's index; its Q15 count
+// stays in out_frac(2 * index).
+template <int L2, class Code> HM_FINL int simt_pick_chroma_mode(const Shared *e, const Simt<L2> &S, uint32_t baseFrac, const int *modeList, Code code)
+{
+  HM_WAVE_FOR(k) {
+    if (k < 10 && !(k & 1)) {
+      const int dirC = chroma_mode_at(modeList, k >> 1);
+      uint32_t frac = baseFrac;
+      simt_bin(e, S, k, &frac, SimtDim<L2>::X_MODE, dirC != DM_CHROMA_IDX);
+      if (dirC != DM_CHROMA_IDX) frac += 2u * 32768u;
+      const int cbfU = S.out_cbf(k), cbfV = S.out_cbf(k + 1);
+      simt_bin(e, S, k, &frac, SimtDim<L2>::X_CBF, cbfU);
+      simt_bin(e, S, k, &frac, SimtDim<L2>::X_CBF, cbfV);
+      if (cbfU) code(k, k, &frac);
+      if (cbfV) code(k, k + 1, &frac);
+      S.out_frac(k) = frac;
+      S.out_cost(k) = calc_rd_cost(e, frac >> 15, S.out_dist(k) + S.out_dist(k + 1));
+    }
+  }
+  HM_SYNC();
+  double bestCost = HM_MAX_DOUBLE; int best = 0;
+  for (int mi = 0; mi < 5; mi++) { const double v = S.out_cost(2 * mi); if (v < bestCost) { bestCost = v; best = mi; } }
+  return HM_UNI(best);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Blocks of 8x8 and 16x16 samples (L2 = 3, 4): the wavefront alternates between two shapes of parallelism,
+//   * sample work (prediction, residual, the transforms, de-quantisation, reconstruction, SSE) one job after the other with the 64 lanes
+//     on the block's samples -- the three passes below, over the batch's transform tile S.tile(stage) with rows of Simt<L2>::TS entries,
+//   * the serial chains (simt_rdoq, simt_code_coeff) for all jobs at once, one job per lane.
+// pred(x, y): the predicted sample.  The transforms are the plain matrix products (rows (32 >> L2) * k of the 32-point matrix): sums of exact
+// integer products, so they give the partial butterflies' integers.
+// ------------------------------------------------------------------------------------------------
+// residual + forward transform (xTrMxN :836); coefficients to A->cs[.][job] in the scan order `scanType`
+template <int L2, class Pred> HM_FINL void simt_residual_fwd(const Simt<L2> &S, const Pel *org, int ps, int bitDepth, int scanType, int job, Pred pred)
+{
+  enum { N = 1 << L2, T = Simt<L2>::TS, ROW = (32 >> L2) * HM_TSTRIDE };
+  int32_t *t0 = S.tile(0), *t1 = S.tile(1);
+  const int s1 = L2 + bitDepth - 9, a1 = 1 << (s1 - 1), s2 = L2 + 6, a2 = 1 << (s2 - 1);
+  HM_PAR_FOR(l, N * N) { const int y = l >> L2, x = l & (N - 1); t0[y * T + x] = org[y * ps + x] - pred(x, y); }
+  HM_SYNC();
+  HM_PAR_FOR(l, N * N) { // first stage
+    const int j = l >> L2, kk = l & (N - 1); int32_t acc = 0;
+    for (int i = 0; i < N; i++) acc += HM_LT()->tmat[kk * ROW + i] * t0[j * T + i];
+    t1[kk * T + j] = (acc + a1) >> s1;
+  }
+  HM_SYNC();
+  HM_PAR_FOR(l, N * N) { // second stage, one lane per scan position
+    const int blkPos = S.scan_pos(scanType, l), kk = blkPos >> L2, j = blkPos & (N - 1); int32_t acc = 0;
+    for (int i = 0; i < N; i++) acc += HM_LT()->tmat[kk * ROW + i] * t1[j * T + i];
+    S.A->cs[l][job] = (int16_t)((acc + a2) >> s2);
+  }
+  HM_SYNC();
+}
+// de-quantisation of job's levels into raster order + first inverse stage (xITrMxN :894); coef: where to store the levels as well, or null
+template <int L2> HM_FINL void simt_dequant_inv1(const Simt<L2> &S, const SimtPar &p, int scanType, int job, int cbf, TCoeff *coef)
+{
+  enum { N = 1 << L2, T = Simt<L2>::TS, ROW = (32 >> L2) * HM_TSTRIDE };
+  int32_t *t0 = S.tile(0), *t1 = S.tile(1);
+  if (cbf) {
+    HM_PAR_FOR(l, N * N) {
+      const int lv = S.lev(l, job), blk = S.scan_pos(scanType, l);
+      if (coef) coef[blk] = lv;
+      t0[(blk >> L2) * T + (blk & (N - 1))] = simt_dequant(p, lv);
+    }
+    HM_SYNC();
+    HM_PAR_FOR(l, N * N) {
+      const int j = l >> L2, i = l & (N - 1); int32_t acc = 0;
+      for (int kk = 0; kk < N; kk++) acc += HM_LT()->tmat[kk * ROW + i] * t0[kk * T + j];
+      t1[j * T + i] = hm_clip3(-32768, 32767, (acc + 64) >> 7);
+    }
+    HM_SYNC();
+  } else if (coef) { HM_PAR_FOR(l, N * N) coef[l] = 0; }
+}
+// second inverse stage + prediction + clip: out(x, y, reconstructed sample)
+template <int L2, class Pred, class Out> HM_FINL void simt_inv2_recon(const Simt<L2> &S, int bitDepth, int cbf, Pred pred, Out out)
+{
+  enum { N = 1 << L2, T = Simt<L2>::TS, ROW = (32 >> L2) * HM_TSTRIDE };
+  const int32_t *t1 = S.tile(1);
+  const int maxv = (1 << bitDepth) - 1, is2 = 20 - bitDepth;
+  HM_PAR_FOR(l, N * N) {
+    const int j = l >> L2, i = l & (N - 1); int resi = 0;
+    if (cbf) {
+      int32_t acc = 0;
+      for (int kk = 0; kk < N; kk++) acc += HM_LT()->tmat[kk * ROW + i] * t1[kk * T + j];
+      resi = hm_clip3(-32768, 32767, (acc + (1 << (is2 - 1))) >> is2);
+    }
+    out(i, j, hm_clip3(0, maxv, pred(i, j) + resi));
+  }
+}
+
+#ifdef HM355_HOSTSIM
+// host twin only: how many candidates the first passes of each size had and how many batches they took (printed at exit when HM355_S16_STATS is set)
+#include <stdio.h>
+struct SimtFirstPassStats {
+  unsigned long cand[2][12], batches[2][4];
+  ~SimtFirstPassStats()
+  {
+    if (!getenv("HM355_S16_STATS")) return;
+    for (int s = 1; s >= 0; s--) {
+      fprintf(stderr, "s%d candidates", 8 << s); for (int i = 0; i < (s ? 8 : 12); i++) fprintf(stderr, " %lu", cand[s][i]);
+      fprintf(stderr, "\ns%d batches", 8 << s); for (int i = 0; i < 4; i++) fprintf(stderr, " %lu", batches[s][i]);
+      fprintf(stderr, "\n");
+    }
+  }
+};
+static SimtFirstPassStats g_first_pass_stats;
+#endif
+
+// the bins every candidate of an unsplit 2Nx2N luma PU codes alike, in front of its own (xEncIntraHeader :965, xEncSubdivCbfQT :856)
+template <int L2> HM_FINL void simt_luma_common_bins(Shared *e, CabacR *r, int cuZ)
+{
+  r->frac &= 32767;
+  if (e->im) { code_skip_flag(e, r, cuZ); enc_bin(e, r, C_PRED_MODE, 1); }
+  if (L2 == 3) enc_bin(e, r, C_PART, 1);                           // 2Nx2N, coded at the smallest CU size only
+  enc_bin(e, r, C_SUBDIV + 5 - L2, 0);                             // transform_split of the root TU: not split in this pass
+}
+
+// ------------------------------------------------------------------------------------------------
+// The first pass of estIntraPredQT (:2473-2490) over the RD candidates e->rdModeList[0..numModes) of the 8x8 or 16x16 luma PU `tv` (a 2Nx2N CU
+// of depth 3 or 2).  Every candidate is the same evaluation of one unsplit transform block from the same CABAC snapshot (xRecurIntraCodingQT
+// with bCheckFirst: no split), and only its cost is kept -- the closing pass picks the winner's evaluation up (simt_luma_winner_as_single_tu)
+// and goes on with the full residual quadtree.  e->cur holds the CU's entry snapshot, e->u.ref the PU's reference samples (both the plain and
+// the smoothed lines), e->mpmPreds its most probable modes.
+// The candidates run in batches of Simt<L2>::JOBS, in list order: member i of a batch (candidate c0 + i) takes slot i, stepping over the slot
+// of the best candidate so far, which stays where it is (its levels, contexts and results are what the closing pass picks up).  Where the
+// largest list fits one batch (Simt<L2>::ONE_BATCH: 8x8) no slot is ever kept, which the compiler knows.
+// Returns the winning mode: the candidate of least cost, the first one on a tie (estIntraPredQT :2520-2560); e->s8Winner: its slot and its
+// place in the list.
+// ------------------------------------------------------------------------------------------------
+template <int L2> HM_DEV HM_NOINLINE int simt_luma_first_pass(Shared *e, TU tv, int numModes)
+{
+  enum { N = 1 << L2, JOBS = Simt<L2>::JOBS, ONE = Simt<L2>::ONE_BATCH };
+  HM_ENTRY(e); numModes = HM_UNI(numModes); tv = hm_uni_struct(tv);
+  const TU *t = &tv;
+  const int ps = e->stride[0], bitDepth = e->bitDepth;
+  const Simt<L2> S(e);
+  uint32_t commonFrac;
+  {
+    CabacR r; cabr_load(e, r, &e->cur);
+    simt_luma_common_bins<L2>(e, &r, t->cuZ);
+    commonFrac = (uint32_t)r.frac;
+  }
+  simt_setup(e, S, &e->cur, ONE || numModes < JOBS ? numModes : JOBS, 0, 1, 1, C_INTRA_LUMA);       // luma cbf at the CU's root TU: context 1
+  const SimtPar p = simt_params<L2>(e, 0);
+  const Pel *org = e->fb.org[0] + (e->ctuY * 64 + t->y) * ps + e->ctuX * 64 + t->x;
+  const int dcVal = ref_dc_val(e, 0, N), shiftSse = (bitDepth - 8) << 1;
+  double bestCost = HM_MAX_DOUBLE; int kept = -1, best = 0;        // kept: the slot of the best candidate so far (none before the first batch)
+#ifdef HM355_HOSTSIM
+  int batchesRun = 0;
+#endif
+  for (int c0 = 0; c0 < numModes;) {
+    const int keep = ONE ? -1 : kept;
+    const int room = keep < 0 ? JOBS : JOBS - 1, nb = ONE || numModes - c0 < room ? numModes - c0 : room;
+    if (keep >= 0) {                                               // fresh context copies for the slots that are used again
+      HM_PAR_FOR(i, SimtDim<L2>::NCTX * JOBS) {
+        const int j = i / JOBS, k = i - j * JOBS;
+        if (k != keep) S.ctx(j, k) = e->cur.s[simt_ctx_index<L2>(j, 0, 1, C_INTRA_LUMA)];
+      }
+      HM_SYNC();
+    }
+    // ---- residual + forward transform of every candidate, lanes on the samples; coefficients to A->cs in the candidate's scan order
+    for (int i = 0; i < nb; i++) {
+      const int slot = i + (keep >= 0 && i >= keep), mode = HM_UNI(e->rdModeList[c0 + i]);
+      simt_residual_fwd(S, org, ps, bitDepth, S.luma_scan(mode), slot, [&](int x, int y) HM_LAMBDA_INL { return pred_sample(e, mode, N, L2, x, y, dcVal, bitDepth); });
+    }
+    // ---- level decision of every candidate, one per lane
+    HM_WAVE_FOR(k) {
+      const int i = (keep >= 0 && k > keep) ? k - 1 : k;
+      if ((ONE || k < JOBS) && k != keep && i < nb) S.out_cbf(k) = (uint8_t)(simt_rdoq(S, p, k, S.luma_scan(e->rdModeList[c0 + i])) > 0);
+    }
+    HM_SYNC();
+    // ---- reconstruction + distortion of every candidate, lanes on the samples
+    for (int i = 0; i < nb; i++) {
+      const int slot = i + (keep >= 0 && i >= keep), mode = HM_UNI(e->rdModeList[c0 + i]), cbf = HM_UNI(S.out_cbf(slot));
+      simt_dequant_inv1(S, p, S.luma_scan(mode), slot, cbf, (TCoeff *)0);
+      uint32_t sse = 0;
+      simt_inv2_recon(S, bitDepth, cbf, [&](int x, int y) HM_LAMBDA_INL { return pred_sample(e, mode, N, L2, x, y, dcVal, bitDepth); },
+                      [&](int x, int y, int r) HM_LAMBDA_INL { const int d = org[y * ps + x] - r; sse += (uint32_t)((d * d) >> shiftSse); });
+      const uint32_t dist = hm_wave_sum(sse);
+      if (hm_lane() == 0) S.out_dist(slot) = dist;
+      HM_SYNC();
+    }
+    // ---- bits and cost of every candidate, one per lane (xGetIntraBitsQT :1038)
+    HM_WAVE_FOR(k) {
+      const int i = (keep >= 0 && k > keep) ? k - 1 : k;
+      if ((ONE || k < JOBS) && k != keep && i < nb) {
+        const int mode = e->rdModeList[c0 + i], cbf = S.out_cbf(k);
+        uint32_t frac = commonFrac;
+        simt_luma_mode_bits(e, S, k, &frac, mode);
+        simt_bin(e, S, k, &frac, SimtDim<L2>::X_CBF, cbf);
+        if (cbf) simt_code_coeff(e, S, k, k, 0, S.luma_scan(mode), &frac);
+        S.out_frac(k) = frac;
+        S.out_cost(k) = calc_rd_cost(e, frac >> 15, S.out_dist(k));
+      }
+    }
+    HM_SYNC();
+    int slotBest = keep;
+    for (int i = 0; i < nb; i++) {                                 // the reference's comparison, in list order: the best so far came earlier in the list
+      const int slot = i + (keep >= 0 && i >= keep); const double v = S.out_cost(slot);
+      if (v < bestCost) { bestCost = v; slotBest = slot; best = c0 + i; }
+    }
+    kept = HM_UNI(slotBest); best = HM_UNI(best);
+    c0 += nb;
+#ifdef HM355_HOSTSIM
+    batchesRun++;
+#endif
+  }
+#ifdef HM355_HOSTSIM
+  { const int top = L2 == 3 ? 11 : 7; g_first_pass_stats.cand[L2 - 3][numModes < top ? numModes : top]++; g_first_pass_stats.batches[L2 - 3][batchesRun < 3 ? batchesRun : 3]++; }
+#endif
+  const int bestMode = HM_UNI(e->rdModeList[best]);
+  e->s8Winner = kept | (best << 8);
+  HM_SYNC();
+  return bestMode;
+}
+
+// The closing pass of estIntraPredQT (:2566-2600) starts with the unsplit evaluation of the winner's transform block -- the very evaluation the
+// first pass made for it, from the same snapshot.  Instead of repeating it (xIntraCodingTUBlock + xGetIntraBitsQT), the winner's results are put
+// where the residual quadtree expects them: levels and reconstruction in the layer buffers of the block's size and in the picture, the estimator
+// (e->cur) advanced past the block's syntax (the bins every candidate codes alike, then the contexts and the bit count of the winner's lane).
+// Must run right after the first pass (the overlays and the reference lines are still in place), with e->cur holding the CU's entry snapshot.
+// Distortion / bits / cbf in e->outDistY / e->outBits / e->outDist.
+template <int L2> HM_DEV HM_NOINLINE void simt_luma_winner_as_single_tu(Shared *e, TU tv)
+{
+  HM_ENTRY(e); tv = hm_uni_struct(tv);
+  const TU *t = &tv; WorkSpace *ws = e->ws;
+  const Simt<L2> S(e);
+  const int won = HM_UNI(e->s8Winner), best = won & 255, z = t->cuZ + t->relZ, ps = e->stride[0], bitDepth = e->bitDepth;
+  const int mode = HM_UNI(e->rdModeList[won >> 8]), cbf = HM_UNI(S.out_cbf(best));
+  const SimtPar p = simt_params<L2>(e, 0);
+  const int dcVal = ref_dc_val(e, 0, 1 << L2);
+  Pel *rq = ws->qtRec[5 - L2] + t->y * 64 + t->x;
+  Pel *recPic = e->fb.rec[0] + (e->ctuY * 64 + t->y) * ps + e->ctuX * 64 + t->x;
+  simt_dequant_inv1(S, p, S.luma_scan(mode), best, cbf, ws->qtCoef[5 - L2] + z * 16);
+  simt_inv2_recon(S, bitDepth, cbf, [&](int x, int y) HM_LAMBDA_INL { return pred_sample(e, mode, 1 << L2, L2, x, y, dcVal, bitDepth); },
+                  [&](int x, int y, int rr) HM_LAMBDA_INL { rq[y * 64 + x] = (Pel)rr; recPic[y * ps + x] = (Pel)rr; });
+  HM_SYNC();
+  { // the estimator: the bins in front of the lane's own (same as the first pass counted), then the lane's contexts and bit count
+    CabacR r; cabr_load(e, r, &e->cur);
+    simt_luma_common_bins<L2>(e, &r, t->cuZ);
+    cabr_store(r, &e->cur);
+  }
+  simt_store_contexts(S, best, &e->cur, 1);
+  e->cur.frac = (uint64_t)S.out_frac(best);
+  e->outDistY = S.out_dist(best); e->outBits = S.out_frac(best) >> 15; e->outDist = (uint32_t)cbf;
+  HM_SYNC();
+}

@@ -50,6 +50,10 @@ template <> struct Simt<2> {              // a batch of 4x4 blocks: RDOQ keeps t
   enum { JOBS = HM_SL, KEEPS_COST = 1 };
   Simt4A *A; Simt4B *B;
   HM_FINL_M explicit Simt(Shared *e) : A((Simt4A *)e->bufA), B((Simt4B *)((char *)&e->u + offsetof(RefLds, refMain))) {}
+  HM_FINL_M uint8_t &out_cbf(int k) const { return A->outCbf[k]; }
+  HM_FINL_M uint32_t &out_dist(int k) const { return A->outDist[k]; }
+  HM_FINL_M uint32_t &out_frac(int k) const { return A->outBits[k]; }        // where a job keeps its Q15 count (simt_pick_chroma_mode)
+  HM_FINL_M double &out_cost(int k) const { return A->outCost[k]; }
   HM_FINL_M int32_t *tab() const { return A->tab; }
   HM_FINL_M uint8_t &ctx(int c, int k) const { return A->ctx[c][k]; }
   HM_FINL_M uint8_t *lps() const { return A->lps; }
@@ -270,8 +274,8 @@ HM_DEV HM_NOINLINE void simt4_luma_pu(Shared *e, TU tv, int numModes)
 // chroma of an 8x8 CU: its one 4x4 block per component under the five chroma modes (estIntraPredChromaQT :2698-2849 over
 // xRecurIntraChromaCodingQT :1958-2145), ten evaluations at once: job 2 * modeIndex + (component - 1).  None of them codes a
 // bin before the mode's bits are counted, so all start from the CU's entry snapshot in e->cur.  Then one lane per mode counts
-// the mode's bits (chroma prediction mode, both cbfs, Cb coefficients, Cr coefficients: xGetIntraBitsQT :1038) on its own
-// context copy, and the modes are compared in the reference's order.  `leaf`: the TU that carries the chroma blocks (the CU's
+// the mode's bits on its own context copy, and the modes are compared in the reference's order (simt_pick_chroma_mode,
+// hm355_simt.h, with the 4x4 coder and the mode's scan).  `leaf`: the TU that carries the chroma blocks (the CU's
 // root TU, or its first 4x4 luma quadrant when the luma transform is split).  Not used when that TU tries transform skip
 // (chroma_tu: the Cr trial then starts from the contexts the Cb winner left, so the evaluations chain).
 // Writes the winner (dirC / cbf / ts of the CU, coefficients, reconstruction into ws->reco) and returns its distortion.
@@ -304,28 +308,11 @@ HM_DEV HM_NOINLINE uint32_t simt4_chroma_cu(Shared *e, TU leafv, int cuZ)
     }
   }
   HM_SYNC();
-  HM_WAVE_FOR(k) {
-    if (k < 10 && !(k & 1)) {                                        // lane 2 * modeIndex: the bits of that mode
-      const int mi = k >> 1;
-      const int dirC = chroma_mode_at(modeList, mi), mode = dirC == DM_CHROMA_IDX ? lumaDir : dirC, scanType = intra_scan_type(mode);
-      uint32_t frac = baseFrac;
-      simt_bin(e, S, k, &frac, SimtDim<2>::X_MODE, dirC != DM_CHROMA_IDX);        // codeIntraDirChroma :692
-      if (dirC != DM_CHROMA_IDX) frac += 2u * 32768u;
-      const int cbfU = A->outCbf[k], cbfV = A->outCbf[k + 1];
-      simt_bin(e, S, k, &frac, SimtDim<2>::X_CBF, cbfU);             // xEncSubdivCbfQT :856: both cbfs at the CU's root TU
-      simt_bin(e, S, k, &frac, SimtDim<2>::X_CBF, cbfV);
-      if (cbfU) s4_code_coeff(e, S, k, k, 1, scanType, 0, &frac);
-      if (cbfV) s4_code_coeff(e, S, k, k + 1, 1, scanType, 0, &frac);
-      const uint32_t bits = frac >> 15, dist = A->outDist[k] + A->outDist[k + 1];
-      A->outBits[k] = dist; A->outBits[k + 1] = frac;                // the odd entries are free: the mode's Q15 count
-      A->outCost[k] = calc_rd_cost(e, bits, dist);
-    }
-  }
-  HM_SYNC();
-  double bestCost = HM_MAX_DOUBLE; int best = 0;
-  for (int mi = 0; mi < 5; mi++) { const double c = A->outCost[2 * mi]; if (c < bestCost) { bestCost = c; best = mi; } }
-  best = HM_UNI(best);
-  const uint32_t bestDist = A->outBits[2 * best];
+  const int best = simt_pick_chroma_mode(e, S, baseFrac, modeList, [&](int k, int src, uint32_t *frac) HM_LAMBDA_INL {
+    const int dirC = chroma_mode_at(modeList, k >> 1);
+    s4_code_coeff(e, S, k, src, 1, intra_scan_type(dirC == DM_CHROMA_IDX ? lumaDir : dirC), 0, frac);
+  });
+  const uint32_t bestDist = A->outDist[2 * best] + A->outDist[2 * best + 1];
   const int cbfU = A->outCbf[2 * best], cbfV = A->outCbf[2 * best + 1];
   HM_WAVE_FOR(k) {
     if ((k >> 1) == best && k < 10) {
@@ -339,7 +326,7 @@ HM_DEV HM_NOINLINE uint32_t simt4_chroma_cu(Shared *e, TU leafv, int cuZ)
     const int vU = t->trDepth ? 3 * cbfU : cbfU, vV = t->trDepth ? 3 * cbfV : cbfV, bm = chroma_mode_at(modeList, best);
     HM_PAR_FOR(i, 4) { m->cbf[1][cuZ + i] = (uint8_t)vU; m->cbf[2][cuZ + i] = (uint8_t)vV; m->ts[1][cuZ + i] = 0; m->ts[2][cuZ + i] = 0; m->dirC[cuZ + i] = (uint8_t)bm; }
   }
-  simt_store_chroma_mode(S, 2 * best, &e->cur, A->outBits[2 * best + 1]);      // e->cur: the estimator after the winning mode's count
+  simt_store_chroma_mode(S, 2 * best, &e->cur, S.out_frac(2 * best));      // e->cur: the estimator after the winning mode's count
   HM_SYNC();
   return bestDist;
 }

@@ -1,7 +1,8 @@
-"""GPU suite (-m gpu): the candidates-in-lanes first pass of 16x16 intra PUs (hm355_simt16.h) on the three launch shapes that reach it -- the
-team kernel with five wavefronts per CTU (one picture), the 12-search kernel with fewWaves == 1 (79 pictures) and with fewWaves == 0 (80
-pictures) -- on the clips of tests/test_simt16_host.py at QP 22 (PUs with 3, 4 and 5 candidates, one and two batches) and on the 128x128 clip
-at QP 4 (the largest levels the 16-bit columns see).  Slot 0 equals the oracle, all slots are equal; every case asserts the shape it ran."""
+"""GPU suite (-m gpu): the candidates-in-lanes first pass of 8x8 and 16x16 intra PUs (simt_luma_first_pass<3> / <4>, hm355_simt.h: one
+function, so the cases pin both sizes) on the three launch shapes that reach it -- the team kernel with five wavefronts per CTU (one picture),
+the 12-search kernel with fewWaves == 1 (79 pictures) and with fewWaves == 0 (80 pictures) -- on the clips of tests/test_simt16_host.py at
+QP 22 (16x16 PUs with 3, 4 and 5 candidates, one and two batches; 8x8 PUs with 8 and with 9 or 10 candidates, one batch) and on the 128x128
+clip at QP 4 (the largest levels the 16-bit columns see).  Slot 0 equals the oracle, all slots are equal; every case asserts the shape it ran."""
 import numpy as np
 import pytest
 

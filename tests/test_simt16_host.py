@@ -1,7 +1,8 @@
-"""The candidates-in-lanes first pass of 16x16 intra PUs (hm355_simt16.h) in the host twin of the kernel source, plain and with every
-lane-parallel loop reversed, against the oracle on fresh synthetic clips: every decision array, cost, coefficient and reconstructed sample
-must be equal.  The twin counts the candidates of each 16x16 first pass and the batches it took (HM355_S16_STATS): the clips must hold PUs
-with 3, 4 and 5 candidates at QP 22, and -- a batch holding four -- PUs that took two batches.  CPU only."""
+"""The candidates-in-lanes first pass of 8x8 and 16x16 intra PUs (simt_luma_first_pass<3> / <4>, hm355_simt.h) in the host twin of the kernel
+source, plain and with every lane-parallel loop reversed, against the oracle on fresh synthetic clips: every decision array, cost, coefficient
+and reconstructed sample must be equal.  The twin counts the candidates of each first pass and the batches it took, per size
+(HM355_S16_STATS): at QP 22 the clips must hold 16x16 PUs with 3, 4 and 5 candidates and -- a 16x16 batch holding four -- PUs that took two
+batches, and 8x8 PUs with 8 and with more than 8 candidates, every one of them in exactly one batch.  CPU only."""
 import os, re, subprocess
 import numpy as np
 import pytest
@@ -45,9 +46,9 @@ def run_twin(exe, clips, clip, qp, wpp, tmp_path):
     dump = tmp_path / "out.bin"
     r = subprocess.run([str(exe), clips[clip][1], str(w), str(h), str(bd), "1", str(qp), str(wpp), str(dump)], check=True,
                        env=dict(os.environ, HM355_S16_STATS="1"), stderr=subprocess.PIPE, text=True)
-    cand = [int(v) for v in re.search(r"s16 candidates((?: \d+)+)", r.stderr).group(1).split()]
-    batches = [int(v) for v in re.search(r"s16 batches((?: \d+)+)", r.stderr).group(1).split()]
-    return gen_golden.parse_dump(str(dump))[0], cand, batches
+    cand, batches, cand8, batches8 = ([int(v) for v in re.search(name + r"((?: \d+)+)", r.stderr).group(1).split()]
+                                      for name in ("s16 candidates", "s16 batches", "s8 candidates", "s8 batches"))
+    return gen_golden.parse_dump(str(dump))[0], cand, batches, cand8, batches8
 
 
 @pytest.mark.parametrize("which", ["plain", "reversed"])
@@ -55,8 +56,8 @@ def run_twin(exe, clips, clip, qp, wpp, tmp_path):
 def test_twin_equals_oracle(twins, clips, tmp_path, which, clip, qp, wpp):
     w, h, _, _ = CLIPS[clip]
     want_rec, want_ctus = reference(clips, clip, qp, wpp)
-    (ctus, rec), cand, batches = run_twin(twins[which], clips, clip, qp, wpp, tmp_path)
-    print(f"{clip} qp{qp} wpp{wpp} {which}: 16x16 first passes by candidates {cand}, by batches {batches}")
+    (ctus, rec), cand, batches, cand8, batches8 = run_twin(twins[which], clips, clip, qp, wpp, tmp_path)
+    print(f"{clip} qp{qp} wpp{wpp} {which}: 16x16 first passes by candidates {cand}, by batches {batches}; 8x8 first passes by candidates {cand8}, by batches {batches8}")
     common.assert_ctus_equal(ctus, want_ctus, f"{clip} qp{qp} wpp{wpp} {which}", (w, h))
     common.assert_rec_equal(want_rec, rec, w, h, "rec")
     assert sum(cand) > 0 and sum(cand) == sum(batches)
@@ -64,13 +65,17 @@ def test_twin_equals_oracle(twins, clips, tmp_path, which, clip, qp, wpp):
         assert cand[3] > 0 and cand[4] > 0 and cand[5] > 0, f"PUs with 3, 4 and 5 candidates must all occur: {cand}"
         assert batches[2] > 0, f"some PU must take two batches (the twin counts the batch loop's iterations): {batches}"
         assert batches[1] == cand[3] + cand[4] and batches[2] == cand[5] + cand[6] and batches[3] == 0, f"a batch holds four, a later one three: {cand} {batches}"
+        assert sum(cand8) > 0, f"8x8 first passes must occur: {cand8}"
+        assert batches8 == [0, sum(cand8), 0, 0], f"every 8x8 first pass takes exactly one batch: {cand8} {batches8}"
+        assert cand8[8] > 0 and sum(cand8[9:]) > 0, f"8x8 PUs with 8 and with more than 8 candidates must both occur: {cand8}"
 
 
 def test_standalone_twin_under_address_and_undefined_sanitizers(clips, tmp_path):
     """the host twin as a stand-alone program built with -fsanitize=address,undefined (host code only) on the first clip at QP 22: no report, same dump as the plain twin's decisions"""
     exe = common.build_hostsim(tmp_path, "hostsim", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", exe="hostsim_san")
     want_rec, want_ctus = reference(clips, "128x128", 22, 1)
-    (ctus, rec), cand, batches = run_twin(exe, clips, "128x128", 22, 1, tmp_path)
+    (ctus, rec), cand, batches, cand8, batches8 = run_twin(exe, clips, "128x128", 22, 1, tmp_path)
     common.assert_ctus_equal(ctus, want_ctus, "sanitized twin", (128, 128))
     common.assert_rec_equal(want_rec, rec, 128, 128, "rec")
     assert cand[3] > 0 and cand[4] > 0 and cand[5] > 0 and batches[2] > 0
+    assert cand8[8] > 0 and sum(cand8[9:]) > 0 and batches8 == [0, sum(cand8), 0, 0]
