@@ -162,7 +162,7 @@ __device__ __forceinline__ double hm_readlane_d(double v, int i)
 
 // optional in-kernel cycle accounting (diagnostic build only: -DHM355_PROFILE, never in the product build)
 #if defined(HM355_PROFILE) && !defined(HM355_HOSTSIM)
-#define HM_PROF_N 45
+#define HM_PROF_N 46
 #define HM_PROF_BEGIN(e, id) const unsigned long long prof_t0_##id = __builtin_readcyclecounter()
 #define HM_PROF_END(e, id) do { (e)->prof[id] += __builtin_readcyclecounter() - prof_t0_##id; (e)->profCnt[id] += 1; } while (0)
 #else
@@ -170,7 +170,7 @@ __device__ __forceinline__ double hm_readlane_d(double v, int i)
 #define HM_PROF_END(e, id) ((void)0)
 #endif
 enum { PR_RDOQ = 0, PR_BITS, PR_ADI, PR_PRED, PR_FWD, PR_INV, PR_SATD35, PR_TUBLK, PR_SAVE, PR_CHROMA, PR_LUMA, PR_ENCCU, PR_TOTAL,
-       PR_S4L = 32, PR_S4C, PR_D0, PR_D1, PR_D2, PR_D3, PR_NXN, PR_S8L, PR_S4LEAF, PR_S4CLEAF, PR_S8C, PR_S16L = 44,
+       PR_S4L = 32, PR_S4C, PR_D0, PR_D1, PR_D2, PR_D3, PR_NXN, PR_S8L, PR_S4LEAF, PR_S4CLEAF, PR_S8C, PR_S16L = 44, PR_SATDL /* the 32x32 and 64x64 calls among PR_SATD35 */,
        PR_ME_INT = 16, PR_ME_FRAC, PR_AMVP, PR_MRG_EST, PR_MC, PR_IRQ, PR_IRES, PR_MRG2N, PR_INTERCU, PR_INTRA_IN_P, PR_IQ_FULL, PR_IQ_FWD, PR_IQ_RDOQ, PR_IQ_BITS, PR_IQ_INV, PR_IQ_ENC };
 
 #define HM_MAX_DOUBLE 1.7e+308
@@ -2021,12 +2021,50 @@ HM_DEV inline void load_intra_result_qt(Shared *e, const TU *t, int comp)
   HM_SYNC();
 }
 
+#ifdef HM355_HOSTSIM
+// host twin only: the 32x32 TUs of the closing passes of 64x64 PUs taken from the first pass's record and those evaluated (printed at exit when HM355_PU64_STATS is set)
+#include <stdio.h>
+struct Pu64ClosingStats {
+  unsigned long n[2];
+  ~Pu64ClosingStats() { if (getenv("HM355_PU64_STATS")) fprintf(stderr, "pu64 closing reused %lu evaluated %lu\n", n[0], n[1]); }
+};
+static Pu64ClosingStats g_pu64_stats;
+#define HM_PU64_STAT(i) ((void)g_pu64_stats.n[i]++)
+#else
+#define HM_PU64_STAT(i) ((void)0)
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // luma residual quadtree (TEncSearch::xRecurIntraCodingQT :1364-1733, bLumaOnly), explicit stack
 // ------------------------------------------------------------------------------------------------
 // returns distortion through *distY and adds the RD cost to *rdCost, exactly like the recursive reference
 HM_DEV HM_NOINLINE void simt4_luma_leaf(Shared *e, TU tv);      // hm355_simt4.h
 template <int L2> HM_DEV HM_NOINLINE void simt_luma_winner_as_single_tu(Shared *e, TU tv);      // hm355_simt.h
+// 32x32 TU k of a 64x64 PU's first-pass candidate: what the closing pass would compute again for it -- distortion, bits, luma cbf and the estimator
+// after its count (e->cur) -- into the set under trial (e->s8Reuse & 1)
+HM_DEV HM_NOINLINE void pu64_record_tu(Shared *e, int k, uint32_t dist, uint32_t bits, int cbf)
+{
+  HM_ENTRY(e); k = HM_UNI(k); dist = HM_UNI(dist); bits = HM_UNI(bits); cbf = HM_UNI(cbf);
+  const int set = e->s8Reuse & 1;
+  if (hm_lane() == 0) { e->ws->pu64[set][k].dist = dist; e->ws->pu64[set][k].bits = bits; e->ws->pu64[set][k].cbf = (uint32_t)cbf; }
+  cabac_copy(&e->ws->pu64Cabac[set][k], &e->cur);
+}
+// ... and the closing pass taking TU k from the winner's set instead of evaluating it: transform depth, skip flag and cbf as intra_coding_tu_block leaves
+// them, the levels and the reconstruction est_intra_pred_qt kept (xSetIntraResultQT) back in the layer buffers, e->cur as intra_bits_qt left it;
+// distortion, bits and cbf come back in e->outDistY, e->outBits and e->outDist
+HM_DEV HM_NOINLINE void pu64_take_tu(Shared *e, TU tv, int k)
+{
+  HM_ENTRY(e); k = HM_UNI(k); tv = hm_uni_struct(tv);
+  const TU *t = &tv; CtuMeta *m = (&e->meta);
+  const int z = t->cuZ + t->relZ, set = e->s8Reuse & 1;
+  par_set8(m->ts[0] + z, 0, t->parts);
+  par_set8(m->tr + z, t->trDepth, t->parts);
+  par_copy32(e->ws->qtCoef[0] + z * 16, e->cc + z * 16, 32 * 32);
+  par_copy_blk(e->ws->qtRec[0] + t->y * 64 + t->x, 64, e->ws->reco + t->y * 64 + t->x, 64, 32);
+  e->outDistY = HM_UNI(e->ws->pu64[set][k].dist); e->outBits = HM_UNI(e->ws->pu64[set][k].bits); e->outDist = HM_UNI(e->ws->pu64[set][k].cbf);
+  par_set8(m->cbf[0] + z, (int)(e->outDist << t->trDepth), t->parts);
+  cabac_copy(&e->cur, &e->ws->pu64Cabac[set][k]);
+}
 HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirst)
 {
   HM_ENTRY(e); checkFirst = HM_UNI(checkFirst); rootv = hm_uni_struct(rootv);
@@ -2034,6 +2072,14 @@ HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirs
   RqtFrame *fr = e->rqt; int sp = 0;
   uint32_t *retDist = e->rqtRetDist, *retBits = e->rqtRetBits; double *retCost = e->rqtRetCost;     // accumulators handed to each level by its parent
   fr[0].t = rootv; fr[0].phase = 0; retDist[0] = 0; retBits[0] = 0; retCost[0] = 0.0;
+  if (rootv.log2 == 6) {
+    // A 64x64 PU has no unsplit form: every candidate is four 32x32 TUs, and the closing pass (:2566-2600) starts with the very evaluations the
+    // winner had in the first pass.  The first pass records them in one of two sets in the workspace (ws->pu64, ws->pu64Cabac), s8Reuse = 4 | the
+    // set under trial; a candidate that beats the best so far (e->outCost: est_intra_pred_qt's own test) leaves its set to the closing pass and
+    // the next one records into the other.  The closing pass takes its TUs from the winner's set, s8Reuse = 6 | set, until one keeps its split.
+    if (checkFirst) { if (!(e->outCost < HM_MAX_DOUBLE)) e->s8Reuse = 4; }      // the PU's first candidate
+    else e->s8Reuse = e->s8Reuse >= 4 ? 6 | ((e->s8Reuse & 1) ^ 1) : 0;
+  }
   while (sp >= 0) {
     RqtFrame *f = &fr[sp]; const TU *t = &f->t;
     const int z = t->cuZ + t->relZ, fullDepth = t->cuDepth + t->trDepth, log2 = t->log2;
@@ -2102,6 +2148,14 @@ HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirs
           par_set8(m->cbf[0] + z, (int)(f->singleCbf << t->trDepth), t->parts);
           f->singleDist = e->outDistY; f->singleCost = e->outRdCost;
           cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(fullDepth, CI_QT_TRAFO_TEST)]);
+        } else if (sp == 1 && e->s8Reuse >= 6) {
+          // closing pass of a 64x64 PU, every earlier 32x32 TU of it unsplit: this one has the inputs it had in the winner's first pass (mode,
+          // neighbours, estimator), so its unsplit form is that evaluation (pu64_take_tu)
+          HM_PU64_STAT(0);
+          if (f->checkSplit) cabac_copy(&e->ws->slot[HM_SLOT(fullDepth, CI_QT_TRAFO_ROOT)], &e->cur);
+          pu64_take_tu(e, *t, fr[0].child - 1);
+          f->singleDist = e->outDistY; f->singleBits = e->outBits; f->singleCbf = e->outDist;
+          f->singleCost = calc_rd_cost(e, f->singleBits, f->singleDist);
         } else {
           if (f->checkSplit) cabac_copy(&e->ws->slot[HM_SLOT(fullDepth, CI_QT_TRAFO_ROOT)], &e->cur);
           par_set8(m->ts[0] + z, 0, t->parts);
@@ -2109,6 +2163,10 @@ HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirs
           if (f->checkSplit) f->singleCbf = (m->cbf[0][z] >> t->trDepth) & 1;
           const uint32_t bits = HM_UCALL(intra_bits_qt(e, *t, 1, 0));
           f->singleCost = calc_rd_cost(e, bits, f->singleDist); f->singleBits = bits;
+          if (sp == 1 && log2 == 5) {
+            if (e->s8Reuse >= 4) pu64_record_tu(e, fr[0].child - 1, f->singleDist, bits, (m->cbf[0][z] >> t->trDepth) & 1);      // first pass of a 64x64 PU
+            else if (!checkFirst) HM_PU64_STAT(1);
+          }
         }
       }
       if (!f->checkSplit) { retDist[sp] += f->singleDist; retBits[sp] += f->singleBits; retCost[sp] += f->singleCost; sp--; continue; }
@@ -2132,6 +2190,7 @@ HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirs
         else if (sp == 0 && !(calc_rd_cost(e, lbBits, retDist[1]) < e->outCost)) {
           // a 64x64 PU (four 32x32 TUs, no unsplit form): the same bound against the best candidate so far, which this one has to beat
           // (estIntraPredQT, TEncSearch.cpp:2490 / :2570) - it cannot, and nothing of it is kept
+          if (e->s8Reuse >= 6) e->s8Reuse = 0;
           e->outDistY = 0; e->outRdCost = HM_MAX_DOUBLE; return;
         }
       }
@@ -2145,7 +2204,10 @@ HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirs
         cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(fullDepth, CI_QT_TRAFO_ROOT)]);
         const uint32_t splitBits = HM_UCALL(intra_bits_qt(e, *t, 1, 0));
         f->splitCost = calc_rd_cost(e, splitBits, f->splitDist);
-        if (f->splitCost < f->singleCost) { retDist[sp] += f->splitDist; retBits[sp] += splitBits; retCost[sp] += f->splitCost; sp--; continue; }
+        if (f->splitCost < f->singleCost) {
+          if (sp == 1 && e->s8Reuse >= 6) e->s8Reuse = 0;   // a 32x32 TU of a 64x64 PU's closing pass keeps its split: the later ones see another reconstruction and estimator than in the first pass
+          retDist[sp] += f->splitDist; retBits[sp] += splitBits; retCost[sp] += f->splitCost; sp--; continue;
+        }
       }
       cabac_copy(&e->cur, &e->ws->slot[HM_SLOT(fullDepth, CI_QT_TRAFO_TEST)]);
       par_set8(m->tr + z, t->trDepth, t->parts);
@@ -2158,6 +2220,7 @@ HM_DEV HM_NOINLINE void recur_intra_coding_qt(Shared *e, TU rootv, int checkFirs
       retDist[sp] += f->singleDist; retBits[sp] += f->singleBits; retCost[sp] += f->singleCost; sp--; continue;
     }
   }
+  if (rootv.log2 == 6) { if (!checkFirst) e->s8Reuse = 0; else if (retCost[0] < e->outCost) e->s8Reuse ^= 1; }
   e->outDistY = retDist[0]; e->outRdCost = retCost[0];
 }
 
@@ -2215,12 +2278,14 @@ HM_DEV HM_NOINLINE uint32_t est_intra_pred_qt(Shared *e, int cuZ, int cuDepth)
       HM_PROF_BEGIN(e, PR_SATD35);
       if (n <= 16) satd_all_modes_small(e, org, ps, n);
       else {
+        HM_PROF_BEGIN(e, PR_SATDL);
         for (int mode = 0; mode < 35; mode++) {
           pred_intra(e, 0, mode, n, use_filtered_refs(0, mode, n), pred, 64);
           const uint32_t sad = dist_hads(org, ps, pred, 64, n, bitDepth);
           if (hm_lane() == 0) e->satd[mode] = sad;
         }
         HM_SYNC();
+        HM_PROF_END(e, PR_SATDL);
       }
       // xUpdateCandList (TEncSearch.cpp:5484-5505) over the 35 modes in order keeps the numModesForFullRD cheapest, a mode going behind
       // the equally cheap ones already listed: the list is the modes sorted by (cost, mode number), cut off.  One lane per mode
@@ -2777,8 +2842,8 @@ template <class M> HM_FINL void cu_walk(Shared *e)
   CtuMeta *m = (&e->meta);
   CuFrame *fr = e->cuf; int sp = 0;
   fr[0].cuZ = 0; fr[0].phase = 0; fr[0].parentPart = SIZE_NONE;
-  double retCost = 0; uint32_t retBits = 0, retDist = 0;
-  M mode;
+  M mode;                                        // a CU returns its result in e->outCost / outBits / outDist: read at once by its parent (phase 2), or the CTU's
+  e->outCost = 0; e->outBits = 0; e->outDist = 0;
   while (sp >= 0) {
     CuFrame *f = &fr[sp]; const int cuDepth = sp, cuZ = f->cuZ;
     const int size = 64 >> cuDepth, parts = 256 >> (2 * cuDepth), q = parts >> 2;
@@ -2787,7 +2852,7 @@ template <class M> HM_FINL void cu_walk(Shared *e)
       const int lx = e->ctuX * 64 + (r & 15) * 4, ty = e->ctuY * 64 + (r >> 4) * 4;
       f->boundary = !((lx + size - 1 < e->width) && (ty + size - 1 < e->height));
       f->bestCost = HM_MAX_DOUBLE; f->bestBits = 0; f->bestDist = 0;
-      if (mode.unsplit(e, f, cuZ, cuDepth)) { retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue; }
+      if (mode.unsplit(e, f, cuZ, cuDepth)) { e->outCost = f->bestCost; e->outBits = f->bestBits; e->outDist = f->bestDist; sp--; continue; }
       init_est_data(e, cuZ, cuDepth);
       f->splitBits = 0; f->splitDist = 0; f->sub = 0; f->phase = 1;
     }
@@ -2826,10 +2891,10 @@ template <class M> HM_FINL void cu_walk(Shared *e)
         f->bestCost = f->splitCost; f->bestBits = f->splitBits; f->bestDist = f->splitDist;
         cabac_copy(&e->ws->slot[HM_SLOT(cuDepth, CI_NEXT_BEST)], &e->ws->slot[HM_SLOT(cuDepth, CI_TEMP_BEST)]);
       } else mode.take_unsplit(e, cuZ, cuDepth);
-      retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--; continue;
+      e->outCost = f->bestCost; e->outBits = f->bestBits; e->outDist = f->bestDist; sp--; continue;
     }
     if (f->phase == 2) { // a sub-CU returned
-      f->splitBits += retBits; f->splitDist += retDist; f->phase = 1;
+      f->splitBits += e->outBits; f->splitDist += e->outDist; f->phase = 1;
       // The split candidate's cost only grows from here (bits and distortion add up, calcRdCost is monotone in both) and it has to come in
       // strictly below the unsplit best (TEncCu.cpp:1704): once the sub-CUs so far are no cheaper, the rest cannot change the decision.
       // One thing of the skipped work does reach outside: the split flag of the parent's split candidate is priced on the estimator "as it
@@ -2848,13 +2913,12 @@ template <class M> HM_FINL void cu_walk(Shared *e)
         }
         if (laterSibling && !(calc_rd_cost(e, f->splitBits, f->splitDist) < f->bestCost)) {
           mode.take_unsplit(e, cuZ, cuDepth);
-          retCost = f->bestCost; retBits = f->bestBits; retDist = f->bestDist; sp--;
+          e->outCost = f->bestCost; e->outBits = f->bestBits; e->outDist = f->bestDist; sp--;
         }
       }
       continue;
     }
   }
-  e->outCost = retCost; e->outBits = retBits; e->outDist = retDist;
 }
 
 // one wavefront searches the CTU: every candidate in place, in the reference's order

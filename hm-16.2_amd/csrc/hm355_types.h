@@ -119,6 +119,10 @@ struct WorkSpace {
   TCoeff teamCoef[HM_COEF_CTU];      // a team helper's private coefficient area (the team's main wavefront works in the picture's own, hm355_team.h)
   InterMeta teamIm;                  // ... and its private copy of the CTU's motion arrays (P / B slices)
   MvD teamTok[3][2][16];             // main wavefront of a team: m_integerMv2Nx2N after the unsplit CU of depth 0..2, where its sub-CUs start from
+  // first pass of a 64x64 intra PU (recur_intra_coding_qt): what each 32x32 TU of the candidate under trial and of the best one so far came to, and the
+  // estimator after its count; two sets of four
+  struct { uint32_t dist, bits, cbf, pad; } pu64[2][4];
+  Cabac pu64Cabac[2][4];
 };
 
 // ---- cu_qp_delta (adaptive QP / rate control; MaxCuDQPDepth 0, i.e. one quantisation group per CTU) ----
