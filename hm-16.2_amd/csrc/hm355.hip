@@ -86,9 +86,11 @@ extern "C" __global__ void __launch_bounds__(64 * HM_CTU_WAVES, 3) hm355_ctu_ker
     if (P->wpp) {
       if (cx > 0) dep0 = a - 1;
       if (cy > 0) dep1 = (cy - 1) * wCtu + (cx + 1 < wCtu ? cx + 1 : cx);
-    } else if (a > 0) dep0 = a - 1;
+    } else if (P->tile) dep0 = P->tile[a].prev;                     // tiles: the CTU before it in its tile, none at the tile's first CTU
+    else if (a > 0) dep0 = a - 1;
     // inter slice: a picture-boundary CTU takes the 2Nx2N integer-MV state of its predecessor in coding order (process_ctu)
-    const int dep2 = (P->wpp && cx == 0 && cy > 0 && P->frames[curItem.frame].imeta && (63 >= P->width || cy * 64 + 63 >= P->height)) ? a - 1 : -1;
+    int dep2 = (P->wpp && cx == 0 && cy > 0 && P->frames[curItem.frame].imeta && (63 >= P->width || cy * 64 + 63 >= P->height)) ? a - 1 : -1;
+    if (P->tile && dep0 < 0 && P->frames[curItem.frame].imeta && (cx * 64 + 63 >= P->width || cy * 64 + 63 >= P->height)) dep2 = P->tile[a].scanPrev;   // ... the last CTU of the tile before
     int bad = 0;
     if (dep0 >= 0) bad = hm355_wait_flag(done + dep0, sched + 1, epoch);
     if (!bad && dep1 >= 0) bad = hm355_wait_flag(done + dep1, sched + 1, epoch);
@@ -133,8 +135,10 @@ extern "C" __global__ void __launch_bounds__(64 * HM_TEAM, 3) hm355_ctu_team_ker
     if (P->wpp) {
       if (cx > 0) dep0 = a - 1;
       if (cy > 0) dep1 = (cy - 1) * wCtu + (cx + 1 < wCtu ? cx + 1 : cx);
-    } else if (a > 0) dep0 = a - 1;
-    const int dep2 = (P->wpp && cx == 0 && cy > 0 && P->frames[T->item.frame].imeta && (63 >= P->width || cy * 64 + 63 >= P->height)) ? a - 1 : -1;   // as in hm355_ctu_kernel
+    } else if (P->tile) dep0 = P->tile[a].prev;
+    else if (a > 0) dep0 = a - 1;
+    int dep2 = (P->wpp && cx == 0 && cy > 0 && P->frames[T->item.frame].imeta && (63 >= P->width || cy * 64 + 63 >= P->height)) ? a - 1 : -1;   // as in hm355_ctu_kernel
+    if (P->tile && dep0 < 0 && P->frames[T->item.frame].imeta && (cx * 64 + 63 >= P->width || cy * 64 + 63 >= P->height)) dep2 = P->tile[a].scanPrev;
     int bad = 0;
     if (dep0 >= 0) bad = hm355_wait_flag(done + dep0, sched + 1, epoch);
     if (!bad && dep1 >= 0) bad = hm355_wait_flag(done + dep1, sched + 1, epoch);
@@ -287,7 +291,13 @@ struct hm355_ctx {
   DevBuf<IngestParams> dIngest; // [max_batch] ingest / output parameters
   DevBuf<int32_t> dIntraCost;  // [numCtus] hm355_intra_cost
   DevBuf<PicStatParams> dPicStat; DevBuf<PicStatAcc> dPicAcc;   // [max_batch] picture statistics: parameters / accumulators
+  // hm355_set_tiles: the layout in force (tiled: more than one tile), its device tables (Params::tile, Params::tileInfo); tileGen counts the
+  // layouts set so far, so that a lane's cached work list and Params are never those of another layout
+  hm355_tile_tables tiles; int tiled = 0, tileGen = 0;
+  DevBuf<TileCtu> dTile; DevBuf<TileInfo> dTileInfo;
 };
+static int num_substreams(const hm355_ctx *c) { return c->tiled ? c->tiles.count() : (c->hp.wpp ? c->hp.hCtu : 1); }
+#define HM_NO_TILES(c, who) do { if ((c)->tiled) return fail((c), HM355_ERR_ARG, who ": not with tiles (hm355_set_tiles): CTU ranges, CTU rows and the cu_qp_delta predictors follow the untiled coding order"); } while (0)
 
 #define HM_CHECK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HM355_ERR_DEVICE; } } while (0)
 
@@ -465,6 +475,11 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   if (rc != HM355_OK) return rc;
   Lane &L = c->lane[l];
   if (L.busy) return fail(c, HM355_ERR_ARG, "hm355_run_begin: the lane still has a launch in flight (hm355_run_wait first)");
+  if (c->tiled) {
+    if (P.wpp) return fail(c, HM355_ERR_ARG, "hm355: tiles with WaveFrontSynchro are not supported (Main / Main10 refuse the combination)");
+    if (ctu0 != 0 || ctu1 != c->numCtus - 1) return fail(c, HM355_ERR_ARG, "hm355: a tiled picture is searched whole (no CTU rows or CTU ranges)");
+    for (int f = 0; f < n; f++) if (c->slots[slot0 + f].dqpOn) return fail(c, HM355_ERR_ARG, "hm355: tiles with cu_qp_delta / rate control are not supported (hm355_set_dqp is armed on a slot)");
+  }
   L.fbs.resize(n);
   for (int f = 0; f < n; f++) {
     if (slices) {
@@ -478,10 +493,12 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   HM_CHECK(c, hipMemcpyAsync(c->dFrames + slot0, L.fbs.data(), sizeof(FrameBuf) * n, hipMemcpyHostToDevice, L.stream));
   int carry = 0;
   for (int f = 0; f < n; f++) carry |= c->slots[slot0 + f].fb.imeta != NULL && (P.height & 63) != 0;
-  const long long key[5] = {slot0, n, carry, ctu0, ctu1};      // the cached work list is reused only for the very same launch shape
+  int carryTiles = 0;
+  for (int f = 0; f < n; f++) carryTiles |= c->slots[slot0 + f].fb.imeta != NULL;
+  const long long key[5] = {slot0, n, carry | carryTiles << 1 | (long long)c->tileGen << 2, ctu0, ctu1};      // the cached work list is reused only for the very same launch shape
   if (!L.keyValid || memcmp(key, L.key, sizeof(key)) != 0) {
     L.keyValid = 0;
-    hm355_build_schedule(P.wCtu, P.hCtu, P.wpp, n, L.items, L.stepStart, carry, slot0, ctu0, ctu1);
+    hm355_build_schedule(P.wCtu, P.hCtu, P.wpp, n, L.items, L.stepStart, carry, slot0, ctu0, ctu1, c->tiled ? &c->tiles : NULL, carryTiles, P.width, P.height);
     HM_CHECK(c, L.dItems.grow(L.items.size()));
     HM_CHECK(c, hipMemcpyAsync(L.dItems, L.items.data(), sizeof(WorkItem) * L.items.size(), hipMemcpyHostToDevice, L.stream));
     memcpy(L.key, key, sizeof(key)); L.keyValid = 1;
@@ -491,19 +508,20 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   for (int f = 0; f < n; f++) if (c->slots[slot0 + f].fb.imeta) anyInter = 1;
   // what a lane's Params must follow: the switches, full search (bit 3) and the ranges above it.  The planner sees bits 0..3: to it full search
   // is one more switch that rules teams out (hm355_host_common.h)
-  const int fastKey = P.esd | P.cfm << 1 | P.ecu << 2 | P.fullSearch << 3 | P.bipredRange << 4 | P.searchRange << 12, fast = fastKey & 15;
+  const int fastKey = (P.esd | P.cfm << 1 | P.ecu << 2 | P.fullSearch << 3 | P.bipredRange << 4 | P.searchRange << 12) ^ c->tileGen << 21, fast = fastKey & 15;
+  const int chains = c->tiled ? c->tiles.count() : 1;
   int envTeam = -1, envTeamWaves = 0;
   { const char *ev = getenv("HM355_TEAM"); if (ev && (ev[0] == '0' || ev[0] == '1')) envTeam = ev[0] - '0'; }
   { const char *ev = getenv("HM355_TEAM_WAVES"); if (ev) envTeamWaves = atoi(ev); }
   const size_t winSamples = (size_t)65 * P.stride[0] + (size_t)33 * (P.stride[1] + P.stride[2]);
-  hm355_launch_plan plan = hm355_plan_launch(P.wCtu, P.hCtu, P.wpp, c->cfg.max_batch, n, ctu0, ctu1, anyInter, fast, envTeam, envTeamWaves, c->laneShare, (long long)L.teamCap);
+  hm355_launch_plan plan = hm355_plan_launch(P.wCtu, P.hCtu, P.wpp, c->cfg.max_batch, n, ctu0, ctu1, anyInter, fast, envTeam, envTeamWaves, c->laneShare, (long long)L.teamCap, chains);
   if ((size_t)plan.wsCount != L.dWs.n || (size_t)plan.total != L.items.size()) return fail(c, HM355_ERR_DEVICE, "hm355: the launch plan does not match the lane");
   if (plan.teamWanted && (size_t)plan.want > L.teamCap) {   // the windows grow only after the lane's stream is idle; without them the launch runs without teams
     HM_CHECK(c, hipStreamSynchronize(L.stream));
     L.teamCap = 0; L.fewWaves = -1;
     if (L.dTeamWin.alloc((size_t)plan.want * HM_TEAM_HELPERS * winSamples) != hipSuccess) (void)hipGetLastError();
     else L.teamCap = (size_t)plan.want;
-    plan = hm355_plan_launch(P.wCtu, P.hCtu, P.wpp, c->cfg.max_batch, n, ctu0, ctu1, anyInter, fast, envTeam, envTeamWaves, c->laneShare, (long long)L.teamCap);
+    plan = hm355_plan_launch(P.wCtu, P.hCtu, P.wpp, c->cfg.max_batch, n, ctu0, ctu1, anyInter, fast, envTeam, envTeamWaves, c->laneShare, (long long)L.teamCap, chains);
   }
   const int fewWaves = plan.fewWaves, waves = plan.waves;
   if (fewWaves != L.fewWaves || fastKey != L.fast) {
@@ -648,6 +666,37 @@ extern "C" int hm355_set_motion_search(hm355_ctx *c, int fast_search, int search
   c->hp.fullSearch = !fast_search; c->hp.searchRange = search_range; c->hp.bipredRange = bipred_search_range;
   return HM355_OK;
 }
+// Tiles (declared in include/hm355.h).  The tables go to the device here; every lane takes the new Params with its next launch (the layout's
+// generation is part of the key its Params are cached under), lane 0 -- whose Params the loop filters and the bitstream pass read -- at once.
+extern "C" int hm355_set_tiles(hm355_ctx *c, int num_cols, const int *col_width_ctus, int num_rows, const int *row_height_ctus, int lf_cross_tile)
+{
+  if (!c) return HM355_ERR_ARG;
+  if (lf_cross_tile != 1) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: lf_cross_tile must be 1 (LFCrossTileBoundaryFlag=0 is not built: the loop filters work across tile edges)");
+  for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: a slice is open (hm355_slice_end first)");
+  for (int l = 0; l < HM_MAX_LANES; l++) if (c->lane[l].busy) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: a launch is in flight (hm355_run_wait first)");
+  hm355_tile_tables t;
+  const char *why = hm355_build_tiles(c->hp.wCtu, c->hp.hCtu, num_cols, col_width_ctus, num_rows, row_height_ctus, &t);
+  if (why) { c->err = std::string("hm355_set_tiles: ") + why; return HM355_ERR_ARG; }
+  const int tiled = t.count() > 1;
+  if (tiled && c->hp.wpp) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: tiles with WaveFrontSynchro are not supported (Main / Main10 refuse the combination)");
+  if (tiled) for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].dqpOn) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: tiles with cu_qp_delta / rate control are not supported (hm355_set_dqp is armed on a slot)");
+  DevBuf<TileCtu> dTile; DevBuf<TileInfo> dInfo;
+  if (tiled) {
+    std::vector<TileInfo> info(t.count());
+    for (int k = 0; k < t.count(); k++) { info[k].firstCtu = t.firstCtu[k]; info[k].scanStart = t.rsToTs[t.firstCtu[k]]; }
+    HM_CHECK(c, dTile.alloc(t.ctu.size())); HM_CHECK(c, dInfo.alloc(info.size()));
+    HM_CHECK(c, hipMemcpy(dTile, t.ctu.data(), sizeof(TileCtu) * t.ctu.size(), hipMemcpyHostToDevice));
+    HM_CHECK(c, hipMemcpy(dInfo, info.data(), sizeof(TileInfo) * info.size(), hipMemcpyHostToDevice));
+  }
+  Params np = c->hp; np.tile = dTile; np.tileInfo = dInfo; np.numTiles = tiled ? t.count() : 0;
+  HM_CHECK(c, hipMemcpy(c->lane[0].dP, &np, sizeof(Params), hipMemcpyHostToDevice));    // nothing is in flight: the old tables have no reader left
+  c->hp = np; c->tiles = t; c->tiled = tiled; c->tileGen = (c->tileGen + 1) & 1023;
+  std::swap(c->dTile.p, dTile.p); std::swap(c->dTile.n, dTile.n); std::swap(c->dTileInfo.p, dInfo.p); std::swap(c->dTileInfo.n, dInfo.n);
+  for (int l = 0; l < HM_MAX_LANES; l++) c->lane[l].keyValid = 0;
+  return HM355_OK;
+}
+extern "C" void hm355_uniform_tiles(int w_ctu, int h_ctu, int num_cols, int num_rows, int *col_width_ctus, int *row_height_ctus)
+{ hm355_tile_uniform_spacing(w_ctu, h_ctu, num_cols, num_rows, col_width_ctus, row_height_ctus); }
 extern "C" int hm355_run_wait(hm355_ctx *c, int lane, double *kernel_ms)
 {
   if (!c || lane < 0 || lane >= HM_MAX_LANES) return HM355_ERR_ARG;
@@ -690,6 +739,7 @@ extern "C" int hm355_set_dqp(hm355_ctx *c, int slot, const hm355_dqp_desc *d)
   if (sl.sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_dqp: a slice is open on the slot (hm355_slice_end first)");
   sl.rcLambda.clear();
   if (!d || !d->use_dqp) { sl.dqpOn = 0; sl.fb.dqp = NULL; sl.ctuQp.clear(); return HM355_OK; }
+  HM_NO_TILES(c, "hm355_set_dqp");
   const int lo = -6 * (c->hp.bitDepth - 8);
   sl.ctuQp.clear();
   if (d->ctu_qp) {
@@ -813,6 +863,7 @@ static int slice_begin_check(hm355_ctx *c, int slot, const hm355_slice_desc *sd)
 extern "C" int hm355_slice_begin(hm355_ctx *c, int slot, const hm355_slice_desc *sd)
 {
   if (!c || !sd || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  HM_NO_TILES(c, "hm355_slice_begin");
   if (sd->slice_type != 2) return fail(c, HM355_ERR_ARG, "hm355_slice_begin: I slices (P / B: hm355_slice_begin_inter)");
   const int rc = slice_begin_check(c, slot, sd);
   if (rc != HM355_OK) return rc;
@@ -823,6 +874,7 @@ extern "C" int hm355_slice_begin(hm355_ctx *c, int slot, const hm355_slice_desc 
 extern "C" int hm355_slice_begin_inter(hm355_ctx *c, int slot, const hm355_inter_slice_desc *sd)
 {
   if (!c || !sd || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
+  HM_NO_TILES(c, "hm355_slice_begin_inter");
   int rc = inter_desc_check(c, sd, "hm355_slice_begin_inter");
   if (rc != HM355_OK) return rc;
   for (int l = 0; l < 2; l++) for (int i = 0; i < sd->num_ref_idx[l]; i++)
@@ -845,6 +897,7 @@ extern "C" int hm355_slice_begin_inter(hm355_ctx *c, int slot, const hm355_inter
 extern "C" int hm355_run_ctus(hm355_ctx *c, int first_slot, int n, int first_ctu, int num_ctus)
 {
   if (!c || n < 1 || first_slot < 0 || first_slot + n > (int)c->slots.size()) return HM355_ERR_ARG;
+  HM_NO_TILES(c, "hm355_run_ctus");
   if (num_ctus < 1 || first_ctu < 0 || first_ctu + num_ctus > c->numCtus) return fail(c, HM355_ERR_ARG, "hm355_run_ctus: bad CTU range");
   for (int f = 0; f < n; f++) {
     const Slot &sl = c->slots[first_slot + f];
@@ -918,6 +971,7 @@ extern "C" int hm355_run(hm355_ctx *c, int n, const hm355_slice_desc *slices)
 extern "C" int hm355_run_rows(hm355_ctx *c, int first_slot, int n, const hm355_slice_desc *slices, int first_row, int last_row)
 {
   if (!c || !slices || n < 1 || first_slot < 0 || first_slot + n > (int)c->slots.size()) return HM355_ERR_ARG;
+  HM_NO_TILES(c, "hm355_run_rows");
   if (first_row < 0 || last_row < first_row || last_row >= c->hp.hCtu) return fail(c, HM355_ERR_ARG, "hm355_run_rows: bad row range");
   if (first_row > 0 && !c->hp.wpp) return fail(c, HM355_ERR_ARG, "hm355_run_rows: a band below the first row needs WaveFrontSynchro=1 (without it the CABAC state chains through every CTU)");
   for (int f = 0; f < n; f++) if (c->slots[first_slot + f].fb.imeta) return fail(c, HM355_ERR_ARG, "hm355_run_rows: I slices only");
@@ -933,6 +987,7 @@ extern "C" size_t hm355_boundary_bytes(const hm355_ctx *c)
 static int boundary_copy(hm355_ctx *c, int slot, int row, void *buf, int toHost)
 {
   if (!c || !buf || slot < 0 || slot >= (int)c->slots.size() || row < 0 || row >= c->hp.hCtu) return HM355_ERR_ARG;
+  HM_NO_TILES(c, "hm355_export_boundary / hm355_import_boundary");
   const Params &P = c->hp; FrameBuf &fb = c->slots[slot].fb;
   uint8_t *p = (uint8_t *)buf;
   const hipMemcpyKind kind = hipMemcpyDefault;       // buf may be host or device memory (a device buffer goes straight to RCCL)
@@ -1492,13 +1547,13 @@ extern "C" int hm355_picture_stats(hm355_ctx *c, hm355_picstat_desc *desc, const
 // ------------------------------------------------------------------------------------------------
 // bitstream pass (TEncSlice::encodeSlice) on the pictures of the slots
 // ------------------------------------------------------------------------------------------------
-extern "C" int hm355_num_substreams(const hm355_ctx *c) { return c ? (c->hp.wpp ? c->hp.hCtu : 1) : HM355_ERR_ARG; }
+extern "C" int hm355_num_substreams(const hm355_ctx *c) { return c ? num_substreams(c) : HM355_ERR_ARG; }
 
 extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *descs)
 {
   if (!c || !descs || n < 1 || n > (int)c->slots.size()) return HM355_ERR_ARG;
   const Params &P = c->hp; Lane &L0 = c->lane[0];
-  const int numSub = P.wpp ? P.hCtu : 1;
+  const int numSub = num_substreams(c), subCap = numSub > P.hCtu ? numSub : P.hCtu;
   const size_t rawBytes = (size_t)c->numCtus * HM_BITS_CAP_PER_CTU;
   std::vector<FrameBuf> fbs(n); std::vector<BitsParams> bps(n);
   next_epoch(c);
@@ -1513,7 +1568,7 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
     }
     if ((d.sao_enabled[0] || d.sao_enabled[1]) && !sl.saoCoded) return fail(c, HM355_ERR_ARG, "hm355_encode_slices_run: the slot holds no SAO parameters (run hm355_sao_run first)");
     HM_CHECK(c, sl.bitsRaw.ensure(rawBytes)); HM_CHECK(c, sl.bitsPacked.ensure(rawBytes));
-    HM_CHECK(c, sl.bitsSizes.ensure(P.hCtu)); HM_CHECK(c, sl.bitsSync.ensure(P.hCtu));
+    HM_CHECK(c, sl.bitsSizes.grow(subCap)); HM_CHECK(c, sl.bitsSync.ensure(P.hCtu));
     HM_CHECK(c, sl.bitsFlag.ensure(P.hCtu, true));
     fbs[f] = sl.fb; fbs[f].imeta = NULL; fbs[f].ip = NULL;
     if (d.slice_type != 2) {
@@ -1531,7 +1586,7 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
     bp.sao = (d.sao_enabled[0] || d.sao_enabled[1]) ? (const int32_t *)sl.saoCoded.p : NULL;
     bp.raw = sl.bitsRaw; bp.capPerCtu = HM_BITS_CAP_PER_CTU; bp.packed = sl.bitsPacked; bp.subSizes = sl.bitsSizes;
     bp.sync = sl.bitsSync; bp.syncFlag = sl.bitsFlag; bp.sched = L0.dSched + 8; bp.epoch = c->epoch; bp.nextInitType = d.slice_type;
-    HM_CHECK(c, hipMemsetAsync(sl.bitsSizes, 0, sizeof(uint32_t) * P.hCtu, L0.stream));     // a substream nobody coded (abandoned launch) has length 0
+    HM_CHECK(c, hipMemsetAsync(sl.bitsSizes, 0, sizeof(uint32_t) * subCap, L0.stream));     // a substream nobody coded (abandoned launch) has length 0
   }
   int rc = stage_slots(c, fbs, c->dBits, bps);
   if (rc != HM355_OK) return rc;

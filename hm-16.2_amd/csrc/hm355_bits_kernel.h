@@ -1,5 +1,5 @@
 // hm355 bitstream pass, part 2: TEncSlice::encodeSlice (TEncSlice.cpp:910-1095) on what the search (and SAO) left in a picture slot.
-// One wavefront codes one substream (the whole slice, or one CTU row under WPP): context initialisation or the WPP hand-off from the
+// One wavefront codes one substream (the whole slice, one CTU row under WPP, or one tile with its CTUs in tile-scan order): context initialisation or the WPP hand-off from the
 // row above, per CTU the SAO syntax (TEncSbac::codeSAOBlkParam :1674) and encode_ctu on the arithmetic coder (hm355_bits.h), then the
 // terminating bin, TEncBinCABAC::finish and the byte alignment.  The wavefront of the last substream also evaluates
 // TEncSbac::determineCabacInitIdx (:163-222).  Substreams of a picture depend on each other only through the WPP context hand-off
@@ -84,7 +84,13 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
   for (int c = 0; c < 3; c++) e->stride[c] = P->stride[c];
   HM_SYNC();
   const int wpp = P->wpp, wCtu = P->wCtu, numCtus = wCtu * P->hCtu;
-  const int first = wpp ? sub * wCtu : 0, last = wpp ? first + wCtu : numCtus;
+  int first = wpp ? sub * wCtu : 0, count = wpp ? wCtu : numCtus, lastSub = first + count == numCtus;
+  // hm355_set_tiles: substream `sub` is tile `sub`, rows [ty0, ..) of columns [tx0, tx0 + tw) in raster order; its bytes go where its place in tile scan says
+  int tw = 0, tx0 = 0, ty0 = 0;
+  if (P->tile) {
+    const TileInfo ti = P->tileInfo[sub]; const TileCtu t = P->tile[ti.firstCtu];
+    tw = t.x1 - t.x0; tx0 = t.x0; ty0 = t.y0; first = ti.scanStart; count = tw * (t.y1 - t.y0); lastSub = sub == P->numTiles - 1;
+  }
   const int initType = bp->sliceType == 2 ? 2 : bp->cabacInitType;     // TEncSbac::resetEntropy :106-115
   const int qp = bp->qp;
   const int maxOffQ = (1 << ((P->bitDepth < 10 ? P->bitDepth : 10) - 5)) - 1;   // g_saoMaxOffsetQVal
@@ -95,7 +101,7 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
   cabw_load_tables(w);
   cabw_start(w);
   w->held = 0; w->numHeld = 0; w->len = 0; w->bins = 0;
-  w->out = bp->raw + (size_t)first * bp->capPerCtu; w->cap = (uint32_t)(last - first) * bp->capPerCtu;
+  w->out = bp->raw + (size_t)first * bp->capPerCtu; w->cap = (uint32_t)count * bp->capPerCtu;
   HM_SYNC();
   if (wpp && sub > 0 && wCtu > 1) {
 #ifndef HM355_HOSTSIM
@@ -119,9 +125,12 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
 #if defined(HM355_PROFILE) && !defined(HM355_HOSTSIM)
   for (int i = 0; i < HM_PROF_N; i++) { e->prof[i] = 0; e->profCnt[i] = 0; }
 #endif
-  for (int a = first; a < last; a++) {
+  for (int k = 0; k < count; k++) {
+    const int a = P->tile ? (ty0 + k / tw) * wCtu + tx0 + k % tw : first + k;
     HM_PROF_BEGIN(e, PR_TOTAL);
     e->ctuX = a % wCtu; e->ctuY = a / wCtu; e->ctuAddr = a;
+    if (P->tile) { e->tileX0 = (uint16_t)(tx0 * 16); e->tileX1 = (uint16_t)((tx0 + tw) * 16); e->tileY0 = (uint16_t)(ty0 * 16); }
+    else { e->tileX0 = 0; e->tileX1 = (uint16_t)(wCtu * 16); e->tileY0 = 0; }
     e->cc = e->fb.coef + (size_t)a * HM_COEF_CTU;
     e->im = e->fb.imeta ? e->fb.imeta + a : (InterMeta *)0;
     { // the decision arrays of the CTU into LDS, where the syntax functions read them
@@ -129,7 +138,7 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
       HM_PAR_FOR(i, (int)(sizeof(CtuMeta) / 4)) dst[i] = src[i];
       HM_SYNC();
     }
-    if (saoOn) bits_sao_blk_param(e, w, bp->sao + (size_t)a * 105, bp->saoEnabled, e->ctuX > 0, e->ctuY > 0, maxOffQ);
+    if (saoOn) bits_sao_blk_param(e, w, bp->sao + (size_t)a * 105, bp->saoEnabled, e->ctuX * 16 > e->tileX0, e->ctuY * 16 > e->tileY0, maxOffQ);   // TComPic::getSAOMergeAvailability: inside the tile
     if (e->fb.dqp) { // cu_qp_delta: the QP the search gave this CTU and its predictor; TEncCu::encodeCtu :358-361 sets m_bEncodeDQP
       const CtuDqp o = e->fb.dqp->out[a];
       if (hm_lane() == 0) { e->ws->dq.ctuQp = o.qp; e->ws->dq.refQp = o.refQp; e->ws->dq.flag = 1; }
@@ -137,7 +146,7 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
     }
     { HM_PROF_BEGIN(e, PR_ENCCU); encode_ctu(e, w, a == numCtus - 1); HM_PROF_END(e, PR_ENCCU); }
     HM_PROF_END(e, PR_TOTAL);
-    if (wpp && a == first + 1) { // m_entropyCodingSyncContextState.loadContexts, TEncSlice.cpp:1050
+    if (wpp && k == 1) { // m_entropyCodingSyncContextState.loadContexts, TEncSlice.cpp:1050
       HM_SYNC();
       CabacW *dst = bp->sync + sub;
       HM_PAR_FOR(i, 192) { dst->s[i] = w->s[i]; dst->used[i] = w->used[i]; }
@@ -167,7 +176,7 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
 #endif
     if (w->len > w->cap) bp->overflow = 1;
   }
-  if (last == numCtus) {
+  if (lastSub) {
     // determineCabacInitIdx :163-222 on the contexts the slice ended with: for the B and the P table, the cost of every context that
     // coded a bin (ContextModel3DBuffer::calcCost); the cheaper table serves the following pictures, B on a tie
     int next = 2;
@@ -202,7 +211,7 @@ __shared__ CabacW g_cabw;
 // The launch owns sched[0] (ticket) and sched[1] (abort), both zeroed by the host in the stream before every launch.
 extern "C" __global__ void __launch_bounds__(64) hm355_bits_kernel(const Params *P, BitsParams *bps, int n, unsigned int *sched)
 {
-  const int numSub = P->wpp ? P->hCtu : 1, total = numSub * n;
+  const int numSub = P->tile ? P->numTiles : (P->wpp ? P->hCtu : 1), total = numSub * n;
   for (;;) {
     // the ticket travels from lane 0 to the wavefront through v_readfirstlane: a scalar value, so the scheduler loop and everything that
     // depends on (row, picture) stay wave-uniform for the compiler as well (handing it over through LDS made the loop "divergent": see DESIGN.md)
@@ -221,11 +230,15 @@ extern "C" __global__ void __launch_bounds__(64) hm355_bits_pack_kernel(const Pa
   if (sched[1] != 0u) return;
   const int sub = (int)blockIdx.x, wCtu = P->wCtu;
   const BitsParams *bp = bps + blockIdx.y;
-  const uint32_t cap = (uint32_t)(P->wpp ? wCtu : wCtu * P->hCtu) * bp->capPerCtu;
-  uint32_t off = 0;
-  for (int k = 0; k < sub; k++) off += bp->subSizes[k] < cap ? bp->subSizes[k] : cap;
+  uint32_t off = 0, cap = 0; int first = 0;
+  for (int k = 0; k <= sub; k++) {
+    int ctus = P->wpp ? wCtu : wCtu * P->hCtu; first = P->wpp ? k * wCtu : 0;
+    if (P->tile) { const TileCtu t = P->tile[P->tileInfo[k].firstCtu]; ctus = (t.x1 - t.x0) * (t.y1 - t.y0); first = P->tileInfo[k].scanStart; }
+    cap = (uint32_t)ctus * bp->capPerCtu;
+    if (k < sub) off += bp->subSizes[k] < cap ? bp->subSizes[k] : cap;
+  }
   uint32_t len = bp->subSizes[sub]; if (len > cap) len = cap;       // an overflowing substream is reported through bp->overflow
-  const uint8_t *src = bp->raw + (size_t)(P->wpp ? sub * wCtu : 0) * bp->capPerCtu;
+  const uint8_t *src = bp->raw + (size_t)first * bp->capPerCtu;
   for (uint32_t i = threadIdx.x; i < len; i += 64) bp->packed[off + i] = src[i];
 }
 #endif

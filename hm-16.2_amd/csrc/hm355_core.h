@@ -387,10 +387,12 @@ struct Shared {
   };
   // uniform per-CTU context
   int32_t width, height, bitDepth, wCtu, stride[3];
+  uint16_t tileX0, tileX1;             // the tile of the CTU under search in 4x4 units: columns [tileX0, tileX1) ... (the picture when it has no tiles)
   const Params *P; FrameBuf fb; WorkSpace *ws; const Tables *tab;
   CtuMeta meta;                        // decision arrays of the CTU under search (written back to HBM at the end)
   TCoeff *cc;
   int32_t ctuX, ctuY, ctuAddr;
+  uint16_t tileY0, tilePad;            // ... and rows from tileY0 on.  What lies outside is unavailable wherever the reference enforces the tile restriction
 #if defined(HM355_PROFILE) && !defined(HM355_HOSTSIM)
   unsigned long long prof[HM_PROF_N]; unsigned long long profCnt[HM_PROF_N];
 #endif
@@ -764,7 +766,7 @@ HM_DEV inline int intra_dir_predictor(const Shared *e, int z, int preds[3])
   const int r = hm_z2r(z);
   const int x4 = e->ctuX * 16 + (r & 15), y4 = e->ctuY * 16 + (r >> 4);
   int left = DC_IDX, above = DC_IDX, zz;
-  if (x4 > 0) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); left = (m->pred[zz] == MODE_INTRA) ? m->dirL[zz] : DC_IDX; }
+  if (x4 > e->tileX0) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); left = (m->pred[zz] == MODE_INTRA) ? m->dirL[zz] : DC_IDX; }
   if ((y4 & 15) != 0) { const CtuMeta *m = meta_at(e, x4, y4 - 1, &zz); above = (m->pred[zz] == MODE_INTRA) ? m->dirL[zz] : DC_IDX; }
   if (left == above) {
     if (left > 1) { preds[0] = left; preds[1] = ((left + 29) % 32) + 2; preds[2] = ((left - 1) % 32) + 2; }
@@ -781,8 +783,8 @@ HM_DEV inline int ctx_split_flag(const Shared *e, int z, int depth)
   const int r = hm_z2r(z);
   const int x4 = e->ctuX * 16 + (r & 15), y4 = e->ctuY * 16 + (r >> 4);
   int ctx = 0, zz;
-  if (x4 > 0) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); ctx += m->depth[zz] > depth; }
-  if (y4 > 0) { const CtuMeta *m = meta_at(e, x4, y4 - 1, &zz); ctx += m->depth[zz] > depth; }
+  if (x4 > e->tileX0) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); ctx += m->depth[zz] > depth; }
+  if (y4 > e->tileY0) { const CtuMeta *m = meta_at(e, x4, y4 - 1, &zz); ctx += m->depth[zz] > depth; }
   return ctx;
 }
 
@@ -795,10 +797,10 @@ HM_DEV inline int avail_above_right(const Shared *e, int rtx4, int rty4, int k)
   const int cx = rtx4 & 15, cy = rty4 & 15;
   if (cx + k <= 15) {
     if (cy != 0) return hm_r2z((cy << 4) | cx) > hm_r2z(((cy - 1) << 4) | (cx + k));
-    return rty4 > 0;
+    return rty4 > e->tileY0;
   }
   if (cy != 0) return 0;
-  return rty4 > 0 && (rtx4 >> 4) < e->wCtu - 1;
+  return rty4 > e->tileY0 && ((rtx4 >> 4) + 1) * 16 < e->tileX1;
 }
 HM_DEV inline int avail_below_left(const Shared *e, int lbx4, int lby4, int k)
 { // TComDataCU::getPUBelowLeftAdi, TComDataCU.cpp:1244-1300
@@ -806,7 +808,7 @@ HM_DEV inline int avail_below_left(const Shared *e, int lbx4, int lby4, int k)
   const int cx = lbx4 & 15, cy = lby4 & 15;
   if (cy + k <= 15) {
     if (cx != 0) return hm_r2z((cy << 4) | cx) > hm_r2z(((cy + k) << 4) | (cx - 1));
-    return lbx4 > 0;
+    return lbx4 > e->tileX0;
   }
   return 0;
 }
@@ -824,10 +826,10 @@ HM_DEV HM_NOINLINE void init_adi_pattern(Shared *e, int comp, int px, int py, in
   int cnt = 0;
   HM_PAR_FOR(u, total) {
     int a;
-    if (u == L) a = (x4 > 0 && y4 > 0);
-    else if (u > L && u <= L + units) a = (y4 > 0);
+    if (u == L) a = (x4 > e->tileX0 && y4 > e->tileY0);
+    else if (u > L && u <= L + units) a = (y4 > e->tileY0);
     else if (u > L + units) a = avail_above_right(e, x4 + units - 1, y4, u - L - units);
-    else if (u >= L - units) a = (x4 > 0);
+    else if (u >= L - units) a = (x4 > e->tileX0);
     else a = avail_below_left(e, x4, y4 + units - 1, L - units - u);
     flags[u] = (uint8_t)a; cnt += a;
   }
@@ -3003,6 +3005,12 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
   e->width = P->width; e->height = P->height; e->bitDepth = P->bitDepth; e->wCtu = P->wCtu; e->mpmZ = -1; e->s8Reuse = 0;
   for (int c = 0; c < 3; c++) e->stride[c] = P->stride[c];
   e->ctuX = it->ctuX; e->ctuY = it->ctuY; e->ctuAddr = it->ctuY * P->wCtu + it->ctuX;
+  // hm355_set_tiles: the tile's edges stand in for the picture's, and the CTU before this one in coding order is the one before it in its tile
+  // (TEncSlice.cpp:724-739); codedPrev -1: the first CTU of a tile (of the picture), where the entropy coder is reset
+  int codedPrev = e->ctuAddr - 1, scanPrev = e->ctuAddr - 1;
+  if (P->tile) { const TileCtu t = P->tile[e->ctuAddr]; e->tileX0 = (uint16_t)(t.x0 * 16); e->tileX1 = (uint16_t)(t.x1 * 16); e->tileY0 = (uint16_t)(t.y0 * 16); codedPrev = t.prev; scanPrev = t.scanPrev; }
+  else { e->tileX0 = 0; e->tileX1 = (uint16_t)(P->wCtu * 16); e->tileY0 = 0; }
+  e->tilePad = 0;
   e->cc = e->fb.coef + (size_t)e->ctuAddr * HM_COEF_CTU;
   e->im = e->fb.imeta ? e->fb.imeta + e->ctuAddr : (InterMeta *)0;
   HM_SYNC();
@@ -3011,7 +3019,8 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
     // overwrites every entry (2Nx2N search at depth 0, all reference indices) before it reads one, so only picture-boundary
     // CTUs take the state of their predecessor -- which is what lets inter slices run as a WPP wavefront.
     const int bnd = it->ctuX * 64 + 63 >= P->width || it->ctuY * 64 + 63 >= P->height;
-    const MvD *src = e->ctuAddr == 0 ? e->fb.ip->integerMv2Nx2N[0] : e->fb.intMv + (size_t)(e->ctuAddr - 1) * 32;
+    // (tiles: it persists in tile scan, so a tile's first CTU takes it from the last CTU of the tile before, which the schedule orders first)
+    const MvD *src = scanPrev < 0 ? e->fb.ip->integerMv2Nx2N[0] : e->fb.intMv + (size_t)scanPrev * 32;
     HM_PAR_FOR(i, 32) { MvD v; v.x = v.y = 0; if (bnd) v = src[i]; e->ws->intMv[i >> 4][i & 15] = v; }
     HM_SYNC();
   }
@@ -3060,7 +3069,7 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
   // CABAC state hand-off (TEncSlice.cpp:733-761)
   Cabac *cb0 = &e->ws->slot[HM_SLOT(0, CI_CURR_BEST)];
   const int initType = e->im ? e->fb.ip->cabacInitType : 2;   // context table of the slice type (TEncSbac::resetEntropy :106-115)
-  if (a == 0) cabac_init(cb0, sliceQp, initType);
+  if (codedPrev < 0) cabac_init(cb0, sliceQp, initType);
   else if (e->ctuX == 0 && P->wpp) {
     cabac_init(cb0, sliceQp, initType);
     if (e->ctuY > 0 && P->wCtu > 1) { // contexts of the 2nd CTU of the row above, fresh bit accumulator
@@ -3068,7 +3077,7 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
       HM_PAR_FOR(i, HM_NUM_CTX) cb0->s[i] = src->s[i];
       HM_SYNC();
     }
-  } else cabac_copy(cb0, e->fb.endState + (a - 1));
+  } else cabac_copy(cb0, e->fb.endState + codedPrev);
   cabac_copy(&e->cur, cb0);
 #if !defined(HM355_HOSTSIM)
   // (a team hands the 64x64 candidate to a helper while it goes on: with m_bEncodeDQP set the later candidates would need to know whether that

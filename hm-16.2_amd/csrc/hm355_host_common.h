@@ -100,6 +100,66 @@ static inline void hm355_intra_lambda(int qp, double *lambda, double *chromaWeig
   *chromaWeight = pow(2.0, (qp - qpc) / 3.0);
 }
 
+// ---- tiles (TComPicSym::initTiles and the address maps above it, TComPicSym.cpp:160-300) ----
+#define HM_MAX_TILE_COLS 20   /* Table A.1: level 6.2 */
+#define HM_MAX_TILE_ROWS 22
+#define HM_MIN_TILE_COLS_CTU 4   /* Main / Main10: a tile is at least 256 luma samples wide and 64 high (TComPicSym.cpp:251-271) */
+// uniform spacing: column c of n over w CTUs is (c + 1) * w / n - c * w / n CTUs wide; rows alike
+static inline void hm355_tile_uniform_spacing(int wCtu, int hCtu, int cols, int rows, int *colWidth, int *rowHeight)
+{
+  for (int c = 0; c < cols; c++) colWidth[c] = (c + 1) * wCtu / cols - c * wCtu / cols;
+  for (int r = 0; r < rows; r++) rowHeight[r] = (r + 1) * hCtu / rows - r * hCtu / rows;
+}
+struct hm355_tile_tables {
+  int cols = 1, rows = 1;
+  std::vector<int> colWidth, rowHeight;   // CTUs
+  std::vector<int> firstCtu;              // [tile] raster address of its first CTU
+  std::vector<int> tileOf;                // [raster address] tile index (tile row * cols + tile column)
+  std::vector<int> rsToTs, tsToRs;        // raster address -> position in tile scan (coding order), and back
+  std::vector<TileCtu> ctu;               // [raster address] what the device reads (Params::tile)
+  int count() const { return cols * rows; }
+};
+// The tables of a layout of cols x rows tiles over wCtu x hCtu CTUs.  Returns NULL, or the reason the layout is refused (then `t` is untouched).
+static inline const char *hm355_build_tiles(int wCtu, int hCtu, int cols, const int *colWidth, int rows, const int *rowHeight, hm355_tile_tables *t)
+{
+  if (cols < 1 || rows < 1 || !colWidth || !rowHeight) return "the layout needs one tile column and one tile row or more, with their widths and heights";
+  if (cols > HM_MAX_TILE_COLS || rows > HM_MAX_TILE_ROWS) return "more than 20 tile columns or 22 tile rows";
+  int sw = 0, sh = 0;
+  for (int c = 0; c < cols; c++) { if (cols > 1 || rows > 1) if (colWidth[c] < HM_MIN_TILE_COLS_CTU) return "a tile column is narrower than 4 CTUs (256 luma samples)"; sw += colWidth[c]; }
+  for (int r = 0; r < rows; r++) { if (rowHeight[r] < 1) return "a tile row is lower than 1 CTU"; sh += rowHeight[r]; }
+  if (sw != wCtu) return "the tile column widths do not sum to the picture's width in CTUs";
+  if (sh != hCtu) return "the tile row heights do not sum to the picture's height in CTUs";
+  hm355_tile_tables o;
+  o.cols = cols; o.rows = rows; o.colWidth.assign(colWidth, colWidth + cols); o.rowHeight.assign(rowHeight, rowHeight + rows);
+  const int n = wCtu * hCtu;
+  o.firstCtu.resize(cols * rows); o.tileOf.resize(n); o.rsToTs.resize(n); o.tsToRs.resize(n); o.ctu.resize(n);
+  int ts = 0, last = -1;
+  for (int r = 0, y0 = 0; r < rows; y0 += rowHeight[r], r++)
+    for (int c = 0, x0 = 0; c < cols; x0 += colWidth[c], c++) {
+      o.firstCtu[r * cols + c] = y0 * wCtu + x0;
+      for (int y = y0; y < y0 + rowHeight[r]; y++)
+        for (int x = x0; x < x0 + colWidth[c]; x++) {
+          const int a = y * wCtu + x;
+          TileCtu e; e.x0 = (int16_t)x0; e.x1 = (int16_t)(x0 + colWidth[c]); e.y0 = (int16_t)y0; e.y1 = (int16_t)(y0 + rowHeight[r]);
+          e.prev = (x == x0 && y == y0) ? -1 : last; e.scanPrev = last;
+          o.ctu[a] = e; o.tileOf[a] = r * cols + c; o.rsToTs[a] = ts; o.tsToRs[ts] = a;
+          last = a; ts++;
+        }
+    }
+  *t = o;
+  return NULL;
+}
+// the first CTU of tile `tile` starts from the m_integerMv2Nx2N of the last CTU of the tile before it (process_ctu): its 64x64 CU crosses the picture edge
+static inline int hm355_tile_carries(const hm355_tile_tables &t, int tile, int width, int height)
+{
+  if (tile == 0) return 0;
+  const int c = tile % t.cols, r = tile / t.cols;
+  int x0 = 0, y0 = 0;
+  for (int i = 0; i < c; i++) x0 += t.colWidth[i];
+  for (int i = 0; i < r; i++) y0 += t.rowHeight[i];
+  return x0 * 64 + 63 >= width || y0 * 64 + 63 >= height;
+}
+
 // Dependency-ordered launch schedule.  Step s holds every CTU whose inputs (left, above-left, above,
 // above-right CTU and the CABAC hand-off) were produced in steps < s:
 //   WaveFrontSynchro=1 : CTU (x,y) runs at step x + 2y   (2-CTU lag wavefront, TEncSlice.cpp:740-755)
@@ -113,15 +173,34 @@ static inline int hm355_schedule_step(int wCtu, int hCtu, int wpp, int carryLast
   if (carryLastRow && hCtu > 1 && wCtu > 1 && y == hCtu - 1) return (wCtu - 1) + 2 * (hCtu - 2) + 1 + x;
   return x + 2 * y;
 }
+// Tiles (never with WaveFrontSynchro): every tile is a chain of its own, a CTU's step is its index inside its tile, and the tiles of a picture are
+// interleaved like the pictures of a batch.  carryTiles (inter slices): a tile whose first CTU starts from the 2Nx2N integer-MV state of the last
+// CTU of the tile before it (hm355_tile_carries; width, height: the picture's) is ordered behind that tile, as carryLastRow does for a WPP row.
 static inline void hm355_build_schedule(int wCtu, int hCtu, int wpp, int nFrames, std::vector<WorkItem> &items, std::vector<int> &stepStart, int carryLastRow = 0,
-                                        int firstFrame = 0, int firstCtu = 0, int lastCtu = -1)
+                                        int firstFrame = 0, int firstCtu = 0, int lastCtu = -1, const hm355_tile_tables *tiles = NULL, int carryTiles = 0,
+                                        int width = 0, int height = 0)
 { // CTUs [firstCtu, lastCtu] (raster addresses, i.e. coding order) of the pictures in slots [firstFrame, firstFrame + nFrames): a band of CTUs (the
   // CTUs before it are complete) -- whole CTU rows (hm355_run_rows), or any range (hm355_run_ctus)
   items.clear(); stepStart.clear();
   if (lastCtu < 0) lastCtu = wCtu * hCtu - 1;
-  const int steps = hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, wCtu - 1, hCtu - 1) + 1;
+  int steps = hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, wCtu - 1, hCtu - 1) + 1;
+  const bool tiled = tiles && tiles->count() > 1;
+  std::vector<int> tileStep;                 // step of every tile's first CTU
+  if (tiled) {
+    tileStep.assign(tiles->count(), 0); steps = 0;
+    for (int t = 0; t < tiles->count(); t++) {
+      const int size = tiles->colWidth[t % tiles->cols] * tiles->rowHeight[t / tiles->cols];
+      if (carryTiles && hm355_tile_carries(*tiles, t, width, height)) tileStep[t] = tileStep[t - 1] + tiles->colWidth[(t - 1) % tiles->cols] * tiles->rowHeight[(t - 1) / tiles->cols];
+      if (tileStep[t] + size > steps) steps = tileStep[t] + size;
+    }
+  }
   std::vector<std::vector<WorkItem> > bucket(steps);
-  for (int a = firstCtu; a <= lastCtu; a++) { const int x = a % wCtu, y = a / wCtu; WorkItem w = {0, x, y, 0}; bucket[hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, x, y)].push_back(w); }
+  for (int a = firstCtu; a <= lastCtu; a++) {
+    const int x = a % wCtu, y = a / wCtu; WorkItem w = {0, x, y, 0};
+    int s = hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, x, y);
+    if (tiled) { const int t = tiles->tileOf[a]; s = tileStep[t] + tiles->rsToTs[a] - tiles->rsToTs[tiles->firstCtu[t]]; }
+    bucket[s].push_back(w);
+  }
   for (int s = 0; s < steps; s++) {
     stepStart.push_back((int)items.size());
     for (int f = 0; f < nFrames; f++) for (size_t i = 0; i < bucket[s].size(); i++) { WorkItem w = bucket[s][i]; w.frame = firstFrame + f; items.push_back(w); }
@@ -133,9 +212,10 @@ static inline void hm355_build_schedule(int wCtu, int hCtu, int wpp, int nFrames
 // needs HM_CTU_WAVES (hm355_core.h), HM_TEAM and HM_TEAM_I (hm355_team.h): both users include hm355_core.h first
 #define HM_WS_MAX 3072   /* 12 searches per CU x 256 CUs is the most that can be resident */
 // the widest step of the dependency schedule: as many CTUs of `frames` pictures as can ever be ready at once
-static inline int hm355_max_items_per_step(int wCtu, int hCtu, int wpp, int frames)
+// chains: independent CABAC chains per picture without WaveFrontSynchro (the tiles of hm355_set_tiles)
+static inline int hm355_max_items_per_step(int wCtu, int hCtu, int wpp, int frames, int chains = 1)
 {
-  if (!wpp) return frames;
+  if (!wpp) return frames * chains;
   int best = 0;
   for (int s = 0; s < wCtu + 2 * (hCtu - 1); s++) { int c = 0; for (int y = 0; y < hCtu; y++) { int x = s - 2 * y; if (x >= 0 && x < wCtu) c++; } if (c > best) best = c; }
   return best * frames;
@@ -161,8 +241,8 @@ struct hm355_launch_plan {
 // among them; fast: esd | cfm << 1 | ecu << 2 | full search << 3; envTeam: HM355_TEAM (-1 unset, 0, 1); envTeamWaves: HM355_TEAM_WAVES (0 unset); laneShare:
 // hm355_set_lane_share; teamCap: teams the lane's reconstruction windows exist for (the caller grows them to `want` and plans again).
 static inline hm355_launch_plan hm355_plan_launch(int wCtu, int hCtu, int wpp, int maxBatch, int n, int ctu0, int ctu1, int anyInter, int fast,
-                                                  int envTeam, int envTeamWaves, int laneShare, long long teamCap)
-{
+                                                  int envTeam, int envTeamWaves, int laneShare, long long teamCap, int chains = 1)
+{ // chains: tiles per picture (1: untiled) -- each is a serial chain of CTUs of its own, so n pictures offer n x chains CTUs at a time
   hm355_launch_plan p; memset(&p, 0, sizeof(p));
   p.wsCount = hm355_ws_count(wCtu * hCtu, maxBatch);
   p.total = n * (ctu1 - ctu0 + 1);
@@ -172,9 +252,9 @@ static inline hm355_launch_plan hm355_plan_launch(int wCtu, int hCtu, int wpp, i
   // P / B slices: a team (nine wavefronts, one team per CU) takes a one-stream picture through 3x faster than one wavefront per CTU, and 256 teams together do about half of
   // what 2,816 one-wavefront searches do: measured on 1080p low-delay P streams with WaveFrontSynchro (CTU/s, one wavefront / teams): 32 streams
   // 798 / 1,556, 64: 1,538 / 2,356, 128: 2,862 / 2,944 -- teams up to 96 streams (1,024 when every stream is one serial chain of CTUs).
-  p.parallel = (long long)n * (wpp ? 16 : 1);
+  p.parallel = (long long)n * (wpp ? 16 : chains);
   p.fewWaves = p.parallel < 1280 ? 1 : 0;
-  int useTeam = (anyInter ? (wpp ? n <= 96 : n <= 1024) : p.parallel <= 512) && p.wsCount >= HM_TEAM;
+  int useTeam = (anyInter ? (wpp ? n <= 96 : p.parallel <= 1024) : p.parallel <= 512) && p.wsCount >= HM_TEAM;
   if (envTeam == 0) useTeam = 0;
   if (envTeam == 1 && p.wsCount >= HM_TEAM) useTeam = 1;
   // hm355_set_fast_decisions: the team protocol starts sub-CUs and partner candidates speculatively, which is not valid once candidates or
@@ -189,7 +269,7 @@ static inline hm355_launch_plan hm355_plan_launch(int wCtu, int hCtu, int wpp, i
   if (useTeam) {
     // as many teams as CTUs can ever be ready at once (the wavefront's widest step), a few more so that a finished team finds the next ticket taken
     const int rows = ctu1 / wCtu - ctu0 / wCtu + 1;
-    long long want = (long long)hm355_max_items_per_step(wCtu, rows < hCtu ? rows : hCtu, wpp, n) + 2;
+    long long want = (long long)hm355_max_items_per_step(wCtu, rows < hCtu ? rows : hCtu, wpp, n, chains) + 2;
     if (want > p.total) want = p.total; if (want > 512) want = 512; if (want > p.wsCount / p.waves) want = p.wsCount / p.waves;
     p.want = (int)want;
     p.teams = (int)(want < teamCap ? want : teamCap);   // without windows (teamCap 0) the launch runs without teams

@@ -178,6 +178,15 @@ struct FrameBuf {
   uint32_t lambdaMotionSAD;          // TComRdCost::m_uiLambdaMotionSAD of the CTU under search (process_ctu: the slice's, or the rate control's for the CTU)
 };
 
+// Tiles (TComPicSym::initTiles, TComPicSym.cpp:198-300): what a CTU search needs of the tile its CTU lies in.  A neighbour in another tile is
+// unavailable to everything spatial (TComDataCU::getPULeft ... with bEnforceTileRestriction), and the CTUs are coded tile after tile
+struct TileCtu {
+  int16_t x0, x1, y0, y1;            // the tile covers CTU columns [x0, x1) and CTU rows [y0, y1)
+  int32_t prev;                      // raster address of the CTU coded before this one in its tile (CABAC hand-off), -1 at the tile's first CTU
+  int32_t scanPrev;                  // ... of the CTU before it in tile scan, whatever its tile (m_integerMv2Nx2N carries on), -1 at the picture's first CTU
+};
+struct TileInfo { int32_t firstCtu, scanStart; };   // raster address of the tile's first CTU; CTUs coded before the tile (its place in tile scan)
+
 struct Params {
   int32_t width, height, bitDepth, wpp;
   int32_t wCtu, hCtu, stride[3];
@@ -193,6 +202,9 @@ struct Params {
   // reference's default, so that a Params that was only zero-filled searches as every launch did before the call existed.
   int32_t fullSearch;                // FastSearch=0: xPatternSearch for uni-prediction too (0: TZ, FastSearch=1)
   int32_t searchRange, bipredRange;  // SearchRange 1..256 (0: 64), BipredSearchRange 1..16 (0: 4)
+  const TileCtu *tile;               // hm355_set_tiles: [numCtus] the tile of every CTU (NULL: one tile, the picture)
+  const TileInfo *tileInfo;          // [numTiles] the tiles in tile-scan order: one substream each (bitstream pass)
+  int32_t numTiles, tilePad;
 };
 
 struct WorkItem { int32_t frame, ctuX, ctuY, pad; };

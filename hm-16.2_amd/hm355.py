@@ -117,7 +117,7 @@ EXPORTS = ["hm355_build_id", "hm355_picture_stats_run", "hm355_picture_stats", "
            "hm355_compress_slice_inter", "hm355_compress_slices_inter", "hm355_deblock", "hm355_deblock_run", "hm355_ref_from_slot", "hm355_ref_release", "hm355_ref_bytes", "hm355_ref_export", "hm355_ref_import", "hm355_sao_run",
            "hm355_num_substreams", "hm355_encode_slices_run", "hm355_encode_slice",
            "hm355_upload_file_frames", "hm355_download_file_frames", "hm355_download_org",
-           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_set_motion_search", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_last_launch_shape", "hm355_dist_batch",
+           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_set_motion_search", "hm355_set_tiles", "hm355_uniform_tiles", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_last_launch_shape", "hm355_dist_batch",
            "hm355_transform_batch"]
 
 
@@ -144,6 +144,9 @@ def load_library(path=LIB_PATH):
     lib.hm355_set_lane_share.argtypes = [C.c_void_p, C.c_int]
     lib.hm355_set_fast_decisions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     lib.hm355_set_motion_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    lib.hm355_set_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.hm355_uniform_tiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.hm355_uniform_tiles.restype = None
     lib.hm355_set_dqp.argtypes = [C.c_void_p, C.c_int, C.POINTER(DqpDesc)]
     lib.hm355_get_dqp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
     lib.hm355_preanalyze.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -434,6 +437,13 @@ class Encoder:
         """the reference's --FastSearch (0 full search, 1 TZ) / --SearchRange (1..256) / --BipredSearchRange (1..16) for every later P / B search of
         this encoder; sticky until set again"""
         self._check(self.lib.hm355_set_motion_search(self.h_, int(fast_search), int(search_range), int(bipred_search_range)), "hm355_set_motion_search")
+
+    def set_tiles(self, col_width_ctus=None, row_height_ctus=None, lf_cross_tile=1):
+        """tiles for every later search, SAO and bitstream pass of this encoder (hm355_set_tiles): the widths of the tile columns and the heights
+        of the tile rows in CTUs, all of them; sticky until set again.  No arguments (or one column and one row): no tiles."""
+        cols = np.ascontiguousarray(col_width_ctus if col_width_ctus is not None else [(self.w + 63) // 64], np.int32)
+        rows = np.ascontiguousarray(row_height_ctus if row_height_ctus is not None else [(self.h + 63) // 64], np.int32)
+        self._check(self.lib.hm355_set_tiles(self.h_, len(cols), cols.ctypes.data, len(rows), rows.ctypes.data, int(lf_cross_tile)), "hm355_set_tiles")
 
     def run_wait(self, lane):
         """wait for the launch of `lane`; returns its kernel time in ms (hm355_run_wait)"""

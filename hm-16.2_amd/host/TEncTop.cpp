@@ -41,6 +41,23 @@ Void TEncTop::create()
     hm355_destroy(m_ctx);
     exit(EXIT_FAILURE);
   }
+  // tiles (TComPicSym::initTiles, TComPicSym.cpp:198-300): uniform spacing, or the configured widths / heights with the last column / row taking the rest
+  if (getNumColumnsMinus1() > 0 || getNumRowsMinus1() > 0) {
+    const Int wCtu = (m_iSourceWidth + 63) / 64, hCtu = (m_iSourceHeight + 63) / 64, nc = getNumColumnsMinus1() + 1, nr = getNumRowsMinus1() + 1;
+    std::vector<Int> cw(nc), rh(nr);
+    if (getTileUniformSpacingFlag()) hm355_uniform_tiles(wCtu, hCtu, nc, nr, cw.data(), rh.data());
+    else {
+      Int restW = wCtu, restH = hCtu;
+      for (Int c = 0; c < nc - 1; c++) { cw[c] = c < (Int)getColumnWidth().size() ? getColumnWidth()[c] : 0; restW -= cw[c]; }
+      for (Int r = 0; r < nr - 1; r++) { rh[r] = r < (Int)getRowHeight().size() ? getRowHeight()[r] : 0; restH -= rh[r]; }
+      cw[nc - 1] = restW; rh[nr - 1] = restH;
+    }
+    if (hm355_set_tiles(m_ctx, nc, cw.data(), nr, rh.data(), getLFCrossTileBoundaryFlag()) != HM355_OK) {
+      fprintf(stderr, "TEncTop::create: %s\n", hm355_last_error(m_ctx));
+      hm355_destroy(m_ctx);
+      exit(EXIT_FAILURE);
+    }
+  }
 }
 Void TEncTop::destroy() { for (auto p : m_cListPic) { if (p->getDeviceRef()) hm355_ref_release(m_ctx, p->getDeviceRef()); delete p; } m_cListPic.clear(); if (m_ctx) hm355_destroy(m_ctx); m_ctx = nullptr; }
 Void TEncTop::init() { m_cGOPEncoder.init(this); m_cSliceEncoder.init(this); m_cLoopFilter.init(this); m_cEncSAO.init(this); }

@@ -132,6 +132,15 @@ public:
   Void setSearchRange(Int i) { m_iSearchRange = i; } Int getSearchRange() const { return m_iSearchRange; }
   Void setBipredSearchRange(Int i) { m_bipredSearchRange = i; } Int getBipredSearchRange() const { return m_bipredSearchRange; }
   Void setUseASR(Bool b) { m_bUseASR = b; } Bool getUseASR() const { return m_bUseASR; }
+  // --TileUniformSpacing, --NumTileColumnsMinus1, --TileColumnWidthArray, --NumTileRowsMinus1, --TileRowHeightArray, --LFCrossTileBoundaryFlag
+  // (TAppEncCfg.cpp:897-903; explicit spacing: all but the last column / row, in CTUs): TEncTop::create lays the tiles out as TComPicSym::initTiles
+  // does and hands them to hm355_set_tiles
+  Void setTileUniformSpacingFlag(Bool b) { m_tileUniformSpacingFlag = b; } Bool getTileUniformSpacingFlag() const { return m_tileUniformSpacingFlag; }
+  Void setNumColumnsMinus1(Int i) { m_iNumColumnsMinus1 = i; } Int getNumColumnsMinus1() const { return m_iNumColumnsMinus1; }
+  Void setNumRowsMinus1(Int i) { m_iNumRowsMinus1 = i; } Int getNumRowsMinus1() const { return m_iNumRowsMinus1; }
+  Void setColumnWidth(const std::vector<Int> &w) { m_tileColumnWidth = w; } const std::vector<Int> &getColumnWidth() const { return m_tileColumnWidth; }
+  Void setRowHeight(const std::vector<Int> &h) { m_tileRowHeight = h; } const std::vector<Int> &getRowHeight() const { return m_tileRowHeight; }
+  Void setLFCrossTileBoundaryFlag(Bool b) { m_bLFCrossTileBoundaryFlag = b; } Bool getLFCrossTileBoundaryFlag() const { return m_bLFCrossTileBoundaryFlag; }
   Int getPad(Int i) const { return m_aiPad[i]; }     // TEncCfg::m_aiPad: the driver feeds pictures of the coded size, so both are 0
   Int getSourceWidth() const { return m_iSourceWidth; } Int getSourceHeight() const { return m_iSourceHeight; }
   Int getQP() const { return m_iQP; } Int getGOPSize() const { return m_iGOPSize; } Int getIntraPeriod() const { return m_uiIntraPeriod; }
@@ -143,6 +152,7 @@ protected:
   Int m_decodedPictureHashSEIEnabled = 0, m_aiPad[2] = { 0, 0 };
   Bool m_useEarlySkipDetection = false, m_bUseCbfFastMode = false, m_bUseEarlyCU = false;
   Int m_iFastSearch = 1, m_iSearchRange = 64, m_bipredSearchRange = 4; Bool m_bUseASR = false;
+  Bool m_tileUniformSpacingFlag = false, m_bLFCrossTileBoundaryFlag = true; Int m_iNumColumnsMinus1 = 0, m_iNumRowsMinus1 = 0; std::vector<Int> m_tileColumnWidth, m_tileRowHeight;
   GOPEntry m_GOPList[16]; Bool m_bUseHADME = true; UInt m_maxNumMergeCand = 5; Int m_TMVPModeId = 1;
 };
 

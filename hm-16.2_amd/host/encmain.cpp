@@ -13,6 +13,8 @@
 //   environment variable HM355_FAST=<esd><cfm><ecu> is read the same way (for callers that build the command line themselves, such as bench.py --workload c3).
 //   ... me=<fast>,<range>,<bipred> as a trailing argument: --FastSearch / --SearchRange / --BipredSearchRange, the integer motion search of P / B slices
 //   (TEncCfg::setFastSearch, setSearchRange, setBipredSearchRange -> hm355_set_motion_search).  The trailing fast=, me= and hash= arguments come in any order.
+//   ... tiles=<cols>x<rows> as a trailing argument: --TileUniformSpacing=1 --NumTileColumnsMinus1 / --NumTileRowsMinus1; tiles=c:<w0,w1,...>;r:<h0,...>: explicit
+//   spacing, every column width and row height in CTUs (TEncCfg::setNumColumnsMinus1, setColumnWidth, ... -> hm355_set_tiles); one substream per tile
 // The slice data of every picture (TEncSlice::encodeSlice) goes to <dump.bin>.bits: per picture u32 numSubstreams, then per substream u32 size + bytes.
 #include "TEncTop.h"
 #include <stdio.h>
@@ -68,6 +70,18 @@ int main(int argc, char **argv)
     int fs, sr, bi; char end;
     if (sscanf(argv[i] + 3, "%d,%d,%d%c", &fs, &sr, &bi, &end) != 3) { fprintf(stderr, "me=<fast>,<range>,<bipred>: three integers\n"); return 2; }
     enc.setFastSearch(fs); enc.setSearchRange(sr); enc.setBipredSearchRange(bi);
+  }
+  for (int i = 9; i < argc; i++) if (!strncmp(argv[i], "tiles=", 6)) {
+    const char *t = argv[i] + 6; int nc = 0, nr = 0; char end;
+    if (sscanf(t, "%dx%d%c", &nc, &nr, &end) == 2 && nc >= 1 && nr >= 1) { enc.setTileUniformSpacingFlag(true); enc.setNumColumnsMinus1(nc - 1); enc.setNumRowsMinus1(nr - 1); }
+    else if (!strncmp(t, "c:", 2) && strstr(t, ";r:")) {
+      std::vector<Int> v[2]; int k = 0;
+      for (const char *p = t + 2; *p;) { if (!strncmp(p, ";r:", 3)) { k = 1; p += 3; continue; } v[k].push_back(atoi(p)); while (*p && *p != ',' && *p != ';') p++; if (*p == ',') p++; }
+      if (v[0].empty() || v[1].empty()) { fprintf(stderr, "tiles=c:<w0,w1,...>;r:<h0,...>: CTU counts\n"); return 2; }
+      enc.setNumColumnsMinus1((Int)v[0].size() - 1); enc.setNumRowsMinus1((Int)v[1].size() - 1);
+      v[0].pop_back(); v[1].pop_back();          // the configuration names all but the last (TAppEncCfg.cpp:1131-1170)
+      enc.setColumnWidth(v[0]); enc.setRowHeight(v[1]);
+    } else { fprintf(stderr, "tiles=<cols>x<rows> or tiles=c:<w0,w1,...>;r:<h0,...>\n"); return 2; }
   }
   enc.create(); enc.init();
   FILE *fs = hashMethod ? fopen((std::string(argv[8]) + ".picstat").c_str(), "w") : NULL;

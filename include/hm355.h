@@ -311,6 +311,23 @@ int hm355_set_fast_decisions(hm355_ctx *ctx, int esd, int cfm, int ecu);
  * HM355_ERR_ARG with a message in hm355_last_error: any other value; a slice open on any slot; a hm355_run_begin launch outstanding.  A
  * rejected call leaves the previous setting in force. */
 int hm355_set_motion_search(hm355_ctx *ctx, int fast_search, int search_range, int bipred_search_range);
+/* Tiles (PPS tiles_enabled_flag; TComPicSym::initTiles, TComPicSym.cpp:198-300): num_cols x num_rows tiles, col_width_ctus[num_cols] and
+ * row_height_ctus[num_rows] in CTUs (all entries, the last ones included).  Sticky and per context like hm355_set_motion_search; 1 x 1 turns
+ * tiles off, which is the state after hm355_create.  The CTUs of a tiled picture are coded tile after tile (tile scan), every tile starts
+ * with fresh CABAC contexts, and a neighbour in another tile is unavailable to the intra reference samples, the most probable modes, the split
+ * and skip flag contexts, the spatial merge / AMVP candidates and the SAO merge candidates; the temporal candidate, the motion search window and
+ * -- lf_cross_tile 1, LFCrossTileBoundaryFlag -- deblocking and the SAO sample classification cross tile edges.  The results stay in raster order;
+ * hm355_num_substreams() becomes num_cols * num_rows and the bitstream pass returns one substream per tile, in tile order.  Every tile is a
+ * chain of CTU searches of its own, so one picture offers num_cols * num_rows CTUs at a time.
+ * HM355_ERR_ARG with a message in hm355_last_error, the previous layout staying in force: widths / heights that do not sum to the picture's size
+ * in CTUs; a column narrower than 4 CTUs or a row lower than 1 (Main / Main10: a tile is at least 256 x 64 luma samples); more than 20 columns
+ * or 22 rows; lf_cross_tile other than 1 (not built); a context with WaveFrontSynchro (Main / Main10 refuse tiles with it); cu_qp_delta armed on
+ * a slot; a slice open on any slot; a hm355_run_begin launch outstanding.  While tiles are on, hm355_set_dqp (arming), hm355_run_rows,
+ * hm355_export_boundary / hm355_import_boundary, hm355_slice_begin(_inter) and hm355_run_ctus are refused: their CTU ranges are raster
+ * addresses and their predictors follow the untiled coding order. */
+int hm355_set_tiles(hm355_ctx *ctx, int num_cols, const int *col_width_ctus, int num_rows, const int *row_height_ctus, int lf_cross_tile);
+/* uniform tile spacing (uniform_spacing_flag): column c of num_cols is (c + 1) * w_ctu / num_cols - c * w_ctu / num_cols CTUs wide, rows alike */
+void hm355_uniform_tiles(int w_ctu, int h_ctu, int num_cols, int num_rows, int *col_width_ctus, int *row_height_ctus);
 
 /* CTU-row bands (TEncSlice.cpp:740-755,855-858 are the WPP hand-off points a band boundary cuts through): a picture is
  * searched by several devices, each owning a band of whole CTU rows [first_row, last_row] of the pictures in slots
