@@ -87,10 +87,12 @@ extern "C" __global__ void __launch_bounds__(64 * HM_CTU_WAVES, 3) hm355_ctu_ker
       if (cx > 0) dep0 = a - 1;
       if (cy > 0) dep1 = (cy - 1) * wCtu + (cx + 1 < wCtu ? cx + 1 : cx);
     } else if (P->tile) dep0 = P->tile[a].prev;                     // tiles: the CTU before it in its tile, none at the tile's first CTU
+    else if (P->slice) dep0 = a > P->slice[a].first ? a - 1 : -1;   // slices: the CTU before it, none at the slice's first CTU
     else if (a > 0) dep0 = a - 1;
     // inter slice: a picture-boundary CTU takes the 2Nx2N integer-MV state of its predecessor in coding order (process_ctu)
     int dep2 = (P->wpp && cx == 0 && cy > 0 && P->frames[curItem.frame].imeta && (63 >= P->width || cy * 64 + 63 >= P->height)) ? a - 1 : -1;
     if (P->tile && dep0 < 0 && P->frames[curItem.frame].imeta && (cx * 64 + 63 >= P->width || cy * 64 + 63 >= P->height)) dep2 = P->tile[a].scanPrev;   // ... the last CTU of the tile before
+    if (P->slice && dep0 < 0 && a > 0 && P->frames[curItem.frame].imeta && (cx * 64 + 63 >= P->width || cy * 64 + 63 >= P->height)) dep2 = a - 1;   // ... of the slice before
     int bad = 0;
     if (dep0 >= 0) bad = hm355_wait_flag(done + dep0, sched + 1, epoch);
     if (!bad && dep1 >= 0) bad = hm355_wait_flag(done + dep1, sched + 1, epoch);
@@ -136,9 +138,11 @@ extern "C" __global__ void __launch_bounds__(64 * HM_TEAM, 3) hm355_ctu_team_ker
       if (cx > 0) dep0 = a - 1;
       if (cy > 0) dep1 = (cy - 1) * wCtu + (cx + 1 < wCtu ? cx + 1 : cx);
     } else if (P->tile) dep0 = P->tile[a].prev;
+    else if (P->slice) dep0 = a > P->slice[a].first ? a - 1 : -1;
     else if (a > 0) dep0 = a - 1;
     int dep2 = (P->wpp && cx == 0 && cy > 0 && P->frames[T->item.frame].imeta && (63 >= P->width || cy * 64 + 63 >= P->height)) ? a - 1 : -1;   // as in hm355_ctu_kernel
     if (P->tile && dep0 < 0 && P->frames[T->item.frame].imeta && (cx * 64 + 63 >= P->width || cy * 64 + 63 >= P->height)) dep2 = P->tile[a].scanPrev;
+    if (P->slice && dep0 < 0 && a > 0 && P->frames[T->item.frame].imeta && (cx * 64 + 63 >= P->width || cy * 64 + 63 >= P->height)) dep2 = a - 1;
     int bad = 0;
     if (dep0 >= 0) bad = hm355_wait_flag(done + dep0, sched + 1, epoch);
     if (!bad && dep1 >= 0) bad = hm355_wait_flag(done + dep1, sched + 1, epoch);
@@ -242,7 +246,7 @@ struct Slot {           // one picture resident in HBM
   DevBuf<InterMeta> imeta;   // motion arrays of the slot (allocated on first inter use; kept for the deblocking pass)
   DevBuf<Pel> saoSrc[3]; DevBuf<SaoStat> saoStat; DevBuf<SaoCand> saoCand; DevBuf<SaoBlk> saoCoded, saoRecon;   // SAO working buffers (allocated on first use)
   DevBuf<uint8_t> rawIn, rawOut;   // file frames as they are on disk (ingest / output, allocated on first use)
-  DevBuf<uint8_t> bitsRaw, bitsPacked; DevBuf<uint32_t> bitsSizes; DevBuf<CabacW> bitsSync; DevBuf<uint32_t> bitsFlag; DevBuf<InterPic> bitsIp;   // bitstream pass (allocated on first use)
+  DevBuf<uint8_t> bitsRaw, bitsPacked; DevBuf<uint32_t> bitsSizes; DevBuf<CabacW> bitsSync; DevBuf<uint32_t> bitsFlag; DevBuf<InterPic> bitsIp; DevBuf<uint32_t> bitsSlice;   // bitstream pass (allocated on first use)
   // cu_qp_delta (hm355_set_dqp): device state of the picture, allocated on first use; dqpOn: the next searches of the slot run with it
   DevBuf<DqpPic> dDqp; DevBuf<int8_t> dCtuQp; DevBuf<CtuDqp> dDqpOut; DevBuf<uint8_t> dRowFlag; int dqpOn = 0, dqpFlagIn = 0;
   std::vector<int8_t> ctuQp; std::vector<uint8_t> rowFlag; hm355_slice_desc lastSlice = {};
@@ -295,8 +299,14 @@ struct hm355_ctx {
   // layouts set so far, so that a lane's cached work list and Params are never those of another layout
   hm355_tile_tables tiles; int tiled = 0, tileGen = 0;
   DevBuf<TileCtu> dTile; DevBuf<TileInfo> dTileInfo;
+  // hm355_set_slices: the partition in force (sliced: more than one slice) and its device tables (Params::slice, Params::sliceStart); a new
+  // partition counts as a new layout (tileGen).  Never together with tiles
+  hm355_slice_tables slicesT; int sliced = 0;
+  DevBuf<SliceCtu> dSlice; DevBuf<int32_t> dSliceStart;
+  std::vector<hm355_slice_bits> sliceBits;   // [slot][slice] of the last hm355_encode_slices_run (hm355_slice_bits_info)
 };
-static int num_substreams(const hm355_ctx *c) { return c->tiled ? c->tiles.count() : (c->hp.wpp ? c->hp.hCtu : 1); }
+static int num_substreams(const hm355_ctx *c) { return c->tiled ? c->tiles.count() : (c->sliced ? c->slicesT.count() : (c->hp.wpp ? c->hp.hCtu : 1)); }
+#define HM_NO_SLICES(c, who) do { if ((c)->sliced) return fail((c), HM355_ERR_ARG, who ": not with slices (hm355_set_slices): CTU ranges, CTU rows and the cu_qp_delta predictors follow the coding order of a one-slice picture"); } while (0)
 #define HM_NO_TILES(c, who) do { if ((c)->tiled) return fail((c), HM355_ERR_ARG, who ": not with tiles (hm355_set_tiles): CTU ranges, CTU rows and the cu_qp_delta predictors follow the untiled coding order"); } while (0)
 
 #define HM_CHECK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); return HM355_ERR_DEVICE; } } while (0)
@@ -480,6 +490,11 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
     if (ctu0 != 0 || ctu1 != c->numCtus - 1) return fail(c, HM355_ERR_ARG, "hm355: a tiled picture is searched whole (no CTU rows or CTU ranges)");
     for (int f = 0; f < n; f++) if (c->slots[slot0 + f].dqpOn) return fail(c, HM355_ERR_ARG, "hm355: tiles with cu_qp_delta / rate control are not supported (hm355_set_dqp is armed on a slot)");
   }
+  if (c->sliced) {
+    if (P.wpp) return fail(c, HM355_ERR_ARG, "hm355: slices with WaveFrontSynchro are not built yet");
+    if (ctu0 != 0 || ctu1 != c->numCtus - 1) return fail(c, HM355_ERR_ARG, "hm355: a picture of several slices is searched whole (no CTU rows or CTU ranges)");
+    for (int f = 0; f < n; f++) if (c->slots[slot0 + f].dqpOn) return fail(c, HM355_ERR_ARG, "hm355: slices with cu_qp_delta / rate control are not supported (hm355_set_dqp is armed on a slot)");
+  }
   L.fbs.resize(n);
   for (int f = 0; f < n; f++) {
     if (slices) {
@@ -498,7 +513,7 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   const long long key[5] = {slot0, n, carry | carryTiles << 1 | (long long)c->tileGen << 2, ctu0, ctu1};      // the cached work list is reused only for the very same launch shape
   if (!L.keyValid || memcmp(key, L.key, sizeof(key)) != 0) {
     L.keyValid = 0;
-    hm355_build_schedule(P.wCtu, P.hCtu, P.wpp, n, L.items, L.stepStart, carry, slot0, ctu0, ctu1, c->tiled ? &c->tiles : NULL, carryTiles, P.width, P.height);
+    hm355_build_schedule(P.wCtu, P.hCtu, P.wpp, n, L.items, L.stepStart, carry, slot0, ctu0, ctu1, c->tiled ? &c->tiles : NULL, carryTiles, P.width, P.height, c->sliced ? &c->slicesT : NULL);
     HM_CHECK(c, L.dItems.grow(L.items.size()));
     HM_CHECK(c, hipMemcpyAsync(L.dItems, L.items.data(), sizeof(WorkItem) * L.items.size(), hipMemcpyHostToDevice, L.stream));
     memcpy(L.key, key, sizeof(key)); L.keyValid = 1;
@@ -509,7 +524,7 @@ static int run_begin(hm355_ctx *c, int l, int slot0, int n, const hm355_slice_de
   // what a lane's Params must follow: the switches, full search (bit 3) and the ranges above it.  The planner sees bits 0..3: to it full search
   // is one more switch that rules teams out (hm355_host_common.h)
   const int fastKey = (P.esd | P.cfm << 1 | P.ecu << 2 | P.fullSearch << 3 | P.bipredRange << 4 | P.searchRange << 12) ^ c->tileGen << 21, fast = fastKey & 15;
-  const int chains = c->tiled ? c->tiles.count() : 1;
+  const int chains = c->tiled ? c->tiles.count() : (c->sliced ? c->slicesT.count() : 1);
   int envTeam = -1, envTeamWaves = 0;
   { const char *ev = getenv("HM355_TEAM"); if (ev && (ev[0] == '0' || ev[0] == '1')) envTeam = ev[0] - '0'; }
   { const char *ev = getenv("HM355_TEAM_WAVES"); if (ev) envTeamWaves = atoi(ev); }
@@ -678,6 +693,7 @@ extern "C" int hm355_set_tiles(hm355_ctx *c, int num_cols, const int *col_width_
   const char *why = hm355_build_tiles(c->hp.wCtu, c->hp.hCtu, num_cols, col_width_ctus, num_rows, row_height_ctus, &t);
   if (why) { c->err = std::string("hm355_set_tiles: ") + why; return HM355_ERR_ARG; }
   const int tiled = t.count() > 1;
+  if (tiled && c->sliced) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: not with slices in force (hm355_set_slices): several slices in a tiled picture are not built");
   if (tiled && c->hp.wpp) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: tiles with WaveFrontSynchro are not supported (Main / Main10 refuse the combination)");
   if (tiled) for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].dqpOn) return fail(c, HM355_ERR_ARG, "hm355_set_tiles: tiles with cu_qp_delta / rate control are not supported (hm355_set_dqp is armed on a slot)");
   DevBuf<TileCtu> dTile; DevBuf<TileInfo> dInfo;
@@ -697,6 +713,38 @@ extern "C" int hm355_set_tiles(hm355_ctx *c, int num_cols, const int *col_width_
 }
 extern "C" void hm355_uniform_tiles(int w_ctu, int h_ctu, int num_cols, int num_rows, int *col_width_ctus, int *row_height_ctus)
 { hm355_tile_uniform_spacing(w_ctu, h_ctu, num_cols, num_rows, col_width_ctus, row_height_ctus); }
+// Slices (declared in include/hm355.h): as hm355_set_tiles -- the tables go to the device here, lane 0's Params at once, the other lanes' with
+// their next launch.
+extern "C" int hm355_set_slices(hm355_ctx *c, int num_slices, const int *first_ctu, int lf_cross_slice)
+{
+  if (!c) return HM355_ERR_ARG;
+  if (lf_cross_slice != 1) return fail(c, HM355_ERR_ARG, "hm355_set_slices: lf_cross_slice must be 1 (LFCrossSliceBoundaryFlag=0 is not built: the loop filters work across slice edges)");
+  for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_slices: a slice is open (hm355_slice_end first)");
+  for (int l = 0; l < HM_MAX_LANES; l++) if (c->lane[l].busy) return fail(c, HM355_ERR_ARG, "hm355_set_slices: a launch is in flight (hm355_run_wait first)");
+  hm355_slice_tables t;
+  const char *why = hm355_build_slices(c->hp.wCtu, c->hp.hCtu, c->hp.wpp, num_slices, first_ctu, &t);
+  if (why) { c->err = std::string("hm355_set_slices: ") + why; return HM355_ERR_ARG; }
+  const int sliced = t.count() > 1;
+  if (sliced && c->tiled) return fail(c, HM355_ERR_ARG, "hm355_set_slices: not with tiles in force (hm355_set_tiles): several slices in a tiled picture are not built");
+  if (sliced && c->hp.wpp) return fail(c, HM355_ERR_ARG, "hm355_set_slices: slices with WaveFrontSynchro are not built yet (the search and the bitstream pass code one substream per slice)");
+  if (sliced) for (size_t s = 0; s < c->slots.size(); s++) if (c->slots[s].dqpOn) return fail(c, HM355_ERR_ARG, "hm355_set_slices: slices with cu_qp_delta / rate control are not supported (hm355_set_dqp is armed on a slot)");
+  DevBuf<SliceCtu> dSlice; DevBuf<int32_t> dStart;
+  if (sliced) {
+    HM_CHECK(c, dSlice.alloc(t.ctu.size())); HM_CHECK(c, dStart.alloc(t.start.size()));
+    HM_CHECK(c, hipMemcpy(dSlice, t.ctu.data(), sizeof(SliceCtu) * t.ctu.size(), hipMemcpyHostToDevice));
+    HM_CHECK(c, hipMemcpy(dStart, t.start.data(), sizeof(int32_t) * t.start.size(), hipMemcpyHostToDevice));
+  }
+  Params np = c->hp; np.slice = dSlice; np.sliceStart = dStart; np.numSlices = sliced ? t.count() : 0;
+  HM_CHECK(c, hipMemcpy(c->lane[0].dP, &np, sizeof(Params), hipMemcpyHostToDevice));    // nothing is in flight: the old tables have no reader left
+  c->hp = np; c->slicesT = t; c->sliced = sliced; c->tileGen = (c->tileGen + 1) & 1023;
+  std::swap(c->dSlice.p, dSlice.p); std::swap(c->dSlice.n, dSlice.n); std::swap(c->dSliceStart.p, dStart.p); std::swap(c->dSliceStart.n, dStart.n);
+  for (int l = 0; l < HM_MAX_LANES; l++) c->lane[l].keyValid = 0;
+  c->sliceBits.clear();
+  return HM355_OK;
+}
+extern "C" int hm355_fixed_ctu_slices(int w_ctu, int h_ctu, int wpp, int ctus_per_slice, int *first_ctu_out, int cap)
+{ return hm355_slice_fixed_ctus(w_ctu, h_ctu, wpp, ctus_per_slice, first_ctu_out, cap); }
+extern "C" int hm355_num_slices(const hm355_ctx *c) { return c ? (c->sliced ? c->slicesT.count() : 1) : HM355_ERR_ARG; }
 extern "C" int hm355_run_wait(hm355_ctx *c, int lane, double *kernel_ms)
 {
   if (!c || lane < 0 || lane >= HM_MAX_LANES) return HM355_ERR_ARG;
@@ -739,7 +787,7 @@ extern "C" int hm355_set_dqp(hm355_ctx *c, int slot, const hm355_dqp_desc *d)
   if (sl.sliceOpen) return fail(c, HM355_ERR_ARG, "hm355_set_dqp: a slice is open on the slot (hm355_slice_end first)");
   sl.rcLambda.clear();
   if (!d || !d->use_dqp) { sl.dqpOn = 0; sl.fb.dqp = NULL; sl.ctuQp.clear(); return HM355_OK; }
-  HM_NO_TILES(c, "hm355_set_dqp");
+  HM_NO_TILES(c, "hm355_set_dqp"); HM_NO_SLICES(c, "hm355_set_dqp");
   const int lo = -6 * (c->hp.bitDepth - 8);
   sl.ctuQp.clear();
   if (d->ctu_qp) {
@@ -863,7 +911,7 @@ static int slice_begin_check(hm355_ctx *c, int slot, const hm355_slice_desc *sd)
 extern "C" int hm355_slice_begin(hm355_ctx *c, int slot, const hm355_slice_desc *sd)
 {
   if (!c || !sd || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
-  HM_NO_TILES(c, "hm355_slice_begin");
+  HM_NO_TILES(c, "hm355_slice_begin"); HM_NO_SLICES(c, "hm355_slice_begin");
   if (sd->slice_type != 2) return fail(c, HM355_ERR_ARG, "hm355_slice_begin: I slices (P / B: hm355_slice_begin_inter)");
   const int rc = slice_begin_check(c, slot, sd);
   if (rc != HM355_OK) return rc;
@@ -874,7 +922,7 @@ extern "C" int hm355_slice_begin(hm355_ctx *c, int slot, const hm355_slice_desc 
 extern "C" int hm355_slice_begin_inter(hm355_ctx *c, int slot, const hm355_inter_slice_desc *sd)
 {
   if (!c || !sd || slot < 0 || slot >= (int)c->slots.size()) return HM355_ERR_ARG;
-  HM_NO_TILES(c, "hm355_slice_begin_inter");
+  HM_NO_TILES(c, "hm355_slice_begin_inter"); HM_NO_SLICES(c, "hm355_slice_begin_inter");
   int rc = inter_desc_check(c, sd, "hm355_slice_begin_inter");
   if (rc != HM355_OK) return rc;
   for (int l = 0; l < 2; l++) for (int i = 0; i < sd->num_ref_idx[l]; i++)
@@ -897,7 +945,7 @@ extern "C" int hm355_slice_begin_inter(hm355_ctx *c, int slot, const hm355_inter
 extern "C" int hm355_run_ctus(hm355_ctx *c, int first_slot, int n, int first_ctu, int num_ctus)
 {
   if (!c || n < 1 || first_slot < 0 || first_slot + n > (int)c->slots.size()) return HM355_ERR_ARG;
-  HM_NO_TILES(c, "hm355_run_ctus");
+  HM_NO_TILES(c, "hm355_run_ctus"); HM_NO_SLICES(c, "hm355_run_ctus");
   if (num_ctus < 1 || first_ctu < 0 || first_ctu + num_ctus > c->numCtus) return fail(c, HM355_ERR_ARG, "hm355_run_ctus: bad CTU range");
   for (int f = 0; f < n; f++) {
     const Slot &sl = c->slots[first_slot + f];
@@ -971,7 +1019,7 @@ extern "C" int hm355_run(hm355_ctx *c, int n, const hm355_slice_desc *slices)
 extern "C" int hm355_run_rows(hm355_ctx *c, int first_slot, int n, const hm355_slice_desc *slices, int first_row, int last_row)
 {
   if (!c || !slices || n < 1 || first_slot < 0 || first_slot + n > (int)c->slots.size()) return HM355_ERR_ARG;
-  HM_NO_TILES(c, "hm355_run_rows");
+  HM_NO_TILES(c, "hm355_run_rows"); HM_NO_SLICES(c, "hm355_run_rows");
   if (first_row < 0 || last_row < first_row || last_row >= c->hp.hCtu) return fail(c, HM355_ERR_ARG, "hm355_run_rows: bad row range");
   if (first_row > 0 && !c->hp.wpp) return fail(c, HM355_ERR_ARG, "hm355_run_rows: a band below the first row needs WaveFrontSynchro=1 (without it the CABAC state chains through every CTU)");
   for (int f = 0; f < n; f++) if (c->slots[first_slot + f].fb.imeta) return fail(c, HM355_ERR_ARG, "hm355_run_rows: I slices only");
@@ -987,7 +1035,7 @@ extern "C" size_t hm355_boundary_bytes(const hm355_ctx *c)
 static int boundary_copy(hm355_ctx *c, int slot, int row, void *buf, int toHost)
 {
   if (!c || !buf || slot < 0 || slot >= (int)c->slots.size() || row < 0 || row >= c->hp.hCtu) return HM355_ERR_ARG;
-  HM_NO_TILES(c, "hm355_export_boundary / hm355_import_boundary");
+  HM_NO_TILES(c, "hm355_export_boundary / hm355_import_boundary"); HM_NO_SLICES(c, "hm355_export_boundary / hm355_import_boundary");
   const Params &P = c->hp; FrameBuf &fb = c->slots[slot].fb;
   uint8_t *p = (uint8_t *)buf;
   const hipMemcpyKind kind = hipMemcpyDefault;       // buf may be host or device memory (a device buffer goes straight to RCCL)
@@ -1554,6 +1602,7 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
   if (!c || !descs || n < 1 || n > (int)c->slots.size()) return HM355_ERR_ARG;
   const Params &P = c->hp; Lane &L0 = c->lane[0];
   const int numSub = num_substreams(c), subCap = numSub > P.hCtu ? numSub : P.hCtu;
+  c->sliceBits.clear();                          // hm355_slice_bits_info has nothing to return unless this call succeeds
   const size_t rawBytes = (size_t)c->numCtus * HM_BITS_CAP_PER_CTU;
   std::vector<FrameBuf> fbs(n); std::vector<BitsParams> bps(n);
   next_epoch(c);
@@ -1570,6 +1619,7 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
     HM_CHECK(c, sl.bitsRaw.ensure(rawBytes)); HM_CHECK(c, sl.bitsPacked.ensure(rawBytes));
     HM_CHECK(c, sl.bitsSizes.grow(subCap)); HM_CHECK(c, sl.bitsSync.ensure(P.hCtu));
     HM_CHECK(c, sl.bitsFlag.ensure(P.hCtu, true));
+    if (c->sliced) HM_CHECK(c, sl.bitsSlice.grow((size_t)3 * numSub));      // per slice: the table it chose, its bins, the flag that publishes both
     fbs[f] = sl.fb; fbs[f].imeta = NULL; fbs[f].ip = NULL;
     if (d.slice_type != 2) {
       HM_CHECK(c, sl.bitsIp.ensure(1));
@@ -1587,6 +1637,10 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
     bp.raw = sl.bitsRaw; bp.capPerCtu = HM_BITS_CAP_PER_CTU; bp.packed = sl.bitsPacked; bp.subSizes = sl.bitsSizes;
     bp.sync = sl.bitsSync; bp.syncFlag = sl.bitsFlag; bp.sched = L0.dSched + 8; bp.epoch = c->epoch; bp.nextInitType = d.slice_type;
     HM_CHECK(c, hipMemsetAsync(sl.bitsSizes, 0, sizeof(uint32_t) * subCap, L0.stream));     // a substream nobody coded (abandoned launch) has length 0
+    if (c->sliced) {
+      bp.sliceNext = (int32_t *)sl.bitsSlice.p; bp.sliceBins = sl.bitsSlice.p + numSub; bp.sliceFlag = sl.bitsSlice.p + 2 * numSub;
+      HM_CHECK(c, hipMemsetAsync(sl.bitsSlice, 0, sizeof(uint32_t) * 3 * numSub, L0.stream));
+    }
   }
   int rc = stage_slots(c, fbs, c->dBits, bps);
   if (rc != HM355_OK) return rc;
@@ -1607,7 +1661,9 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
   HM_CHECK(c, hipMemcpy(bps.data(), c->dBits, sizeof(BitsParams) * n, hipMemcpyDeviceToHost));
   unsigned int bs[2] = {0, 0};
   HM_CHECK(c, hipMemcpy(bs, bsched, sizeof(bs), hipMemcpyDeviceToHost));
-  if (bs[1]) return fail(c, HM355_ERR_DEVICE, "bitstream pass: a WPP hand-off wait was abandoned");
+  if (bs[1]) return fail(c, HM355_ERR_DEVICE, "bitstream pass: a wait for the WPP hand-off or for the slice before was abandoned");
+  const int numSlices = c->sliced ? numSub : 1;
+  std::vector<hm355_slice_bits> sliceBits((size_t)c->slots.size() * numSlices, hm355_slice_bits());
   for (int f = 0; f < n; f++) {
     hm355_bits_desc &d = descs[f]; Slot &sl = c->slots[f];
     if (bps[f].overflow) return fail(c, HM355_ERR_DEVICE, "bitstream pass: a substream outgrew its buffer");
@@ -1616,8 +1672,24 @@ extern "C" int hm355_encode_slices_run(hm355_ctx *c, int n, hm355_bits_desc *des
     if (tot > d.out_cap) return fail(c, HM355_ERR_ARG, "hm355_encode_slices_run: out_cap too small");
     if (tot) HM_CHECK(c, hipMemcpy(d.out, sl.bitsPacked, tot, hipMemcpyDeviceToHost));
     d.next_cabac_init_type = bps[f].nextInitType; d.num_bins = bps[f].bins;
+    hm355_slice_bits *sb = &sliceBits[(size_t)f * numSlices];
+    if (c->sliced) {
+      std::vector<uint32_t> v((size_t)2 * numSub);
+      HM_CHECK(c, hipMemcpy(v.data(), sl.bitsSlice, sizeof(uint32_t) * v.size(), hipMemcpyDeviceToHost));
+      for (int k = 0; k < numSub; k++) { sb[k].num_substreams = 1; sb[k].next_cabac_init_type = (int32_t)v[k]; sb[k].num_bins = v[numSub + k]; }
+    } else { sb[0].num_substreams = numSub; sb[0].next_cabac_init_type = bps[f].nextInitType; sb[0].num_bins = bps[f].bins; }
   }
+  c->sliceBits.swap(sliceBits);
   return HM355_OK;
+}
+
+extern "C" int hm355_slice_bits_info(const hm355_ctx *c, int slot, hm355_slice_bits *out, int cap)
+{
+  if (!c || slot < 0 || slot >= (int)c->slots.size() || (cap > 0 && !out)) return HM355_ERR_ARG;
+  const int numSlices = c->sliced ? c->slicesT.count() : 1;
+  if (c->sliceBits.size() != c->slots.size() * (size_t)numSlices) return HM355_ERR_ARG;       // no bitstream pass since the partition was set
+  for (int k = 0; k < numSlices && k < cap; k++) out[k] = c->sliceBits[(size_t)slot * numSlices + k];
+  return numSlices;
 }
 
 // host buffers in: the CTU data of one slice goes to slot 0 first

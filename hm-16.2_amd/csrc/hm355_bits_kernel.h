@@ -1,9 +1,11 @@
 // hm355 bitstream pass, part 2: TEncSlice::encodeSlice (TEncSlice.cpp:910-1095) on what the search (and SAO) left in a picture slot.
-// One wavefront codes one substream (the whole slice, one CTU row under WPP, or one tile with its CTUs in tile-scan order): context initialisation or the WPP hand-off from the
+// One wavefront codes one substream (the whole slice, one CTU row under WPP, one tile with its CTUs in tile-scan order, or one slice of hm355_set_slices): context initialisation or the WPP hand-off from the
 // row above, per CTU the SAO syntax (TEncSbac::codeSAOBlkParam :1674) and encode_ctu on the arithmetic coder (hm355_bits.h), then the
 // terminating bin, TEncBinCABAC::finish and the byte alignment.  The wavefront of the last substream also evaluates
 // TEncSbac::determineCabacInitIdx (:163-222).  Substreams of a picture depend on each other only through the WPP context hand-off
-// (after the second CTU of the row above), published through a flag per row.
+// (after the second CTU of the row above), published through a flag per row -- and, with hm355_set_slices, through the context table: slice k of
+// a P / B picture starts from the table slice k - 1 chose (determineCabacInitIdx at the end of every encodeSlice, read by the next resetEntropy),
+// published through a flag per slice.
 #pragma once
 
 struct BitsParams {                   // one picture of the batch
@@ -17,6 +19,8 @@ struct BitsParams {                   // one picture of the batch
   uint32_t *sched;                    // per launch, shared by the pictures of the batch: [0] ticket counter, [1] abort word
   uint32_t epoch;
   int32_t nextInitType; uint32_t bins; int32_t overflow;    // results
+  // hm355_set_slices: [numSlices] what determineCabacInitIdx chose at the end of every slice, its bins, and a flag == epoch once both are published
+  int32_t *sliceNext; uint32_t *sliceBins; uint32_t *sliceFlag;
 };
 
 HM_CONST uint8_t HM_SAO_INIT[3][2] = { {153, 160}, {153, 185}, {153, 200} };   // [B, P, I][merge, type]: INIT_SAO_MERGE_FLAG / INIT_SAO_TYPE_IDX, ContextTables.h
@@ -75,7 +79,26 @@ HM_DEV inline void bits_sao_blk_param(const Shared *e, CabacW *w, const int32_t 
   if (!isLeft && !isAbove) for (int c = 0; c < 3; c++) bits_sao_offset_param(e, w, c, blk + c * 35, sliceEnabled[c], maxOffQ);
 }
 
-// one substream of one picture.  Returns non-zero when a WPP wait was abandoned (device only).
+#ifndef HM355_HOSTSIM
+// waits until *flag == the launch's epoch (agent scope), as the search waits for its dependencies; non-zero (wave-uniform) when the wait was abandoned
+HM_DEV inline int bits_wait_flag(BitsParams *bp, const uint32_t *flag)
+{
+  int bad = 0;
+  if (hm_lane() == 0) {
+    const unsigned long long t0 = wall_clock64();
+    while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != bp->epoch) {
+      __builtin_amdgcn_s_sleep(16);
+      if (__hip_atomic_load(bp->sched + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || wall_clock64() - t0 > 10ull * 100000000ull) {
+        __hip_atomic_store(bp->sched + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); bad = 1; break;   // every workgroup of the launch drains
+      }
+    }
+  }
+  if (__shfl(bad, 0, 64)) return 1;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  return 0;
+}
+#endif
+// one substream of one picture.  Returns non-zero when a wait (WPP hand-off, the slice before) was abandoned (device only).
 HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, int frame, BitsParams *bp, int sub, int wsIndex)
 {
   // uniform context (every lane writes the same values), as process_ctu sets it up for the search
@@ -91,7 +114,20 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
     const TileInfo ti = P->tileInfo[sub]; const TileCtu t = P->tile[ti.firstCtu];
     tw = t.x1 - t.x0; tx0 = t.x0; ty0 = t.y0; first = ti.scanStart; count = tw * (t.y1 - t.y0); lastSub = sub == P->numTiles - 1;
   }
-  const int initType = bp->sliceType == 2 ? 2 : bp->cabacInitType;     // TEncSbac::resetEntropy :106-115
+  int initType = bp->sliceType == 2 ? 2 : bp->cabacInitType;     // TEncSbac::resetEntropy :106-115
+  // hm355_set_slices: substream `sub` is slice `sub`, CTUs [sliceStart[sub], sliceStart[sub + 1]).  A P / B slice after the first starts from the
+  // context table the slice before it chose (PPS m_encCABACTableIdx, TEncSlice.cpp:1083-1093 -> TEncSbac.cpp:106-115): its ticket, item - n, was
+  // taken earlier, so the wait ends.  I slices have no such chain
+  const int sliced = P->slice != 0;
+  if (sliced) {
+    first = P->sliceStart[sub]; count = P->sliceStart[sub + 1] - first; lastSub = sub == P->numSlices - 1;
+    if (sub > 0 && bp->sliceType != 2) {
+#ifndef HM355_HOSTSIM
+      if (bits_wait_flag(bp, bp->sliceFlag + (sub - 1))) return 1;
+#endif
+      initType = bp->sliceNext[sub - 1];
+    }
+  }
   const int qp = bp->qp;
   const int maxOffQ = (1 << ((P->bitDepth < 10 ? P->bitDepth : 10) - 5)) - 1;   // g_saoMaxOffsetQVal
   const int saoOn = bp->sao && (bp->saoEnabled[0] || bp->saoEnabled[1]);
@@ -105,18 +141,7 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
   HM_SYNC();
   if (wpp && sub > 0 && wCtu > 1) {
 #ifndef HM355_HOSTSIM
-    int bad = 0;
-    if (hm_lane() == 0) {
-      const unsigned long long t0 = wall_clock64();
-      while (__hip_atomic_load(bp->syncFlag + (sub - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != bp->epoch) {
-        __builtin_amdgcn_s_sleep(16);
-        if (__hip_atomic_load(bp->sched + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || wall_clock64() - t0 > 10ull * 100000000ull) {
-          __hip_atomic_store(bp->sched + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); bad = 1; break;   // every workgroup of the launch drains
-        }
-      }
-    }
-    if (__shfl(bad, 0, 64)) return 1;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (bits_wait_flag(bp, bp->syncFlag + (sub - 1))) return 1;
 #endif
     const CabacW *src = bp->sync + (sub - 1);
     HM_PAR_FOR(i, 192) { w->s[i] = src->s[i]; w->used[i] = src->used[i]; }
@@ -131,6 +156,7 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
     e->ctuX = a % wCtu; e->ctuY = a / wCtu; e->ctuAddr = a;
     if (P->tile) { e->tileX0 = (uint16_t)(tx0 * 16); e->tileX1 = (uint16_t)((tx0 + tw) * 16); e->tileY0 = (uint16_t)(ty0 * 16); }
     else { e->tileX0 = 0; e->tileX1 = (uint16_t)(wCtu * 16); e->tileY0 = 0; }
+    e->otherSlice = sliced ? (uint16_t)((a - 1 < first ? 1 : 0) | (a - wCtu < first ? 2 : 0) | (a - wCtu - 1 < first ? 4 : 0) | (a - wCtu + 1 < first ? 8 : 0)) : (uint16_t)0;
     e->cc = e->fb.coef + (size_t)a * HM_COEF_CTU;
     e->im = e->fb.imeta ? e->fb.imeta + a : (InterMeta *)0;
     { // the decision arrays of the CTU into LDS, where the syntax functions read them
@@ -138,13 +164,13 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
       HM_PAR_FOR(i, (int)(sizeof(CtuMeta) / 4)) dst[i] = src[i];
       HM_SYNC();
     }
-    if (saoOn) bits_sao_blk_param(e, w, bp->sao + (size_t)a * 105, bp->saoEnabled, e->ctuX * 16 > e->tileX0, e->ctuY * 16 > e->tileY0, maxOffQ);   // TComPic::getSAOMergeAvailability: inside the tile
+    if (saoOn) bits_sao_blk_param(e, w, bp->sao + (size_t)a * 105, bp->saoEnabled, e->ctuX * 16 > e->tileX0 && !(e->otherSlice & 1), e->ctuY * 16 > e->tileY0 && !(e->otherSlice & 2), maxOffQ);   // TComPic::getSAOMergeAvailability: inside the tile and the slice
     if (e->fb.dqp) { // cu_qp_delta: the QP the search gave this CTU and its predictor; TEncCu::encodeCtu :358-361 sets m_bEncodeDQP
       const CtuDqp o = e->fb.dqp->out[a];
       if (hm_lane() == 0) { e->ws->dq.ctuQp = o.qp; e->ws->dq.refQp = o.refQp; e->ws->dq.flag = 1; }
       HM_SYNC();
     }
-    { HM_PROF_BEGIN(e, PR_ENCCU); encode_ctu(e, w, a == numCtus - 1); HM_PROF_END(e, PR_ENCCU); }
+    { HM_PROF_BEGIN(e, PR_ENCCU); encode_ctu(e, w, sliced ? k == count - 1 : a == numCtus - 1); HM_PROF_END(e, PR_ENCCU); }
     HM_PROF_END(e, PR_TOTAL);
     if (wpp && k == 1) { // m_entropyCodingSyncContextState.loadContexts, TEncSlice.cpp:1050
       HM_SYNC();
@@ -176,7 +202,7 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
 #endif
     if (w->len > w->cap) bp->overflow = 1;
   }
-  if (lastSub) {
+  if (lastSub || sliced) {
     // determineCabacInitIdx :163-222 on the contexts the slice ended with: for the B and the P table, the cost of every context that
     // coded a bin (ContextModel3DBuffer::calcCost); the cheaper table serves the following pictures, B on a tie
     int next = 2;
@@ -197,7 +223,15 @@ HM_DEV inline int bits_encode_substream(Shared *e, CabacW *w, const Params *P, i
       cost[0] = hm_wave_sum(cost[0]); cost[1] = hm_wave_sum(cost[1]);
       next = cost[1] < cost[0] ? 1 : 0;
     }
-    if (hm_lane() == 0) bp->nextInitType = next;
+    if (hm_lane() == 0 && lastSub) bp->nextInitType = next;
+    if (sliced) { // the slice's own values, then the flag the next slice of the picture waits for
+      if (hm_lane() == 0) { bp->sliceNext[sub] = next; bp->sliceBins[sub] = w->bins; }
+#ifndef HM355_HOSTSIM
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      if (hm_lane() == 0) __hip_atomic_store(bp->sliceFlag + sub, bp->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+    }
   }
   return 0;
 }
@@ -211,7 +245,7 @@ __shared__ CabacW g_cabw;
 // The launch owns sched[0] (ticket) and sched[1] (abort), both zeroed by the host in the stream before every launch.
 extern "C" __global__ void __launch_bounds__(64) hm355_bits_kernel(const Params *P, BitsParams *bps, int n, unsigned int *sched)
 {
-  const int numSub = P->tile ? P->numTiles : (P->wpp ? P->hCtu : 1), total = numSub * n;
+  const int numSub = P->tile ? P->numTiles : (P->slice ? P->numSlices : (P->wpp ? P->hCtu : 1)), total = numSub * n;
   for (;;) {
     // the ticket travels from lane 0 to the wavefront through v_readfirstlane: a scalar value, so the scheduler loop and everything that
     // depends on (row, picture) stay wave-uniform for the compiler as well (handing it over through LDS made the loop "divergent": see DESIGN.md)
@@ -234,6 +268,7 @@ extern "C" __global__ void __launch_bounds__(64) hm355_bits_pack_kernel(const Pa
   for (int k = 0; k <= sub; k++) {
     int ctus = P->wpp ? wCtu : wCtu * P->hCtu; first = P->wpp ? k * wCtu : 0;
     if (P->tile) { const TileCtu t = P->tile[P->tileInfo[k].firstCtu]; ctus = (t.x1 - t.x0) * (t.y1 - t.y0); first = P->tileInfo[k].scanStart; }
+    if (P->slice) { first = P->sliceStart[k]; ctus = P->sliceStart[k + 1] - first; }
     cap = (uint32_t)ctus * bp->capPerCtu;
     if (k < sub) off += bp->subSizes[k] < cap ? bp->subSizes[k] : cap;
   }

@@ -392,7 +392,9 @@ struct Shared {
   CtuMeta meta;                        // decision arrays of the CTU under search (written back to HBM at the end)
   TCoeff *cc;
   int32_t ctuX, ctuY, ctuAddr;
-  uint16_t tileY0, tilePad;            // ... and rows from tileY0 on.  What lies outside is unavailable wherever the reference enforces the tile restriction
+  uint16_t tileY0, otherSlice;         // ... and rows from tileY0 on.  What lies outside is unavailable wherever the reference enforces the tile restriction.
+                                       // otherSlice (hm355_set_slices): the neighbouring CTUs that belong to another slice -- 1 left, 2 above, 4 above-left,
+                                       // 8 above-right -- and are unavailable in the same places (bEnforceSliceRestriction); 0 without slices
 #if defined(HM355_PROFILE) && !defined(HM355_HOSTSIM)
   unsigned long long prof[HM_PROF_N]; unsigned long long profCnt[HM_PROF_N];
 #endif
@@ -761,12 +763,21 @@ HM_DEV inline const CtuMeta *meta_at(const Shared *e, int x4, int y4, int *z)
 { *z = hm_r2z(((y4 & 15) << 4) | (x4 & 15)); const int ca = (y4 >> 4) * e->wCtu + (x4 >> 4); return ca == e->ctuAddr ? &e->meta : e->fb.meta + ca; }
 
 // TComDataCU::getIntraDirPredictor, TComDataCU.cpp:1513-1586 (luma)
+// hm355_set_slices: the 4x4 unit (gx, gy) of the picture lies in a neighbouring CTU -- left of, or in the CTU row above, the CTU under search --
+// that belongs to another slice (TComDataCU::getPULeft / getPUAbove / getPUAboveLeft / getPUAboveRight with bEnforceSliceRestriction)
+HM_DEV inline int in_other_slice(const Shared *e, int gx, int gy)
+{
+  if (!e->otherSlice) return 0;
+  const int dx = (gx >> 4) - e->ctuX, dy = (gy >> 4) - e->ctuY;
+  const int bit = dy == 0 ? (dx < 0 ? 1 : 0) : (dy < 0 ? (dx < 0 ? 4 : (dx == 0 ? 2 : 8)) : 0);
+  return e->otherSlice & bit;
+}
 HM_DEV inline int intra_dir_predictor(const Shared *e, int z, int preds[3])
 {
   const int r = hm_z2r(z);
   const int x4 = e->ctuX * 16 + (r & 15), y4 = e->ctuY * 16 + (r >> 4);
   int left = DC_IDX, above = DC_IDX, zz;
-  if (x4 > e->tileX0) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); left = (m->pred[zz] == MODE_INTRA) ? m->dirL[zz] : DC_IDX; }
+  if (x4 > e->tileX0 && !in_other_slice(e, x4 - 1, y4)) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); left = (m->pred[zz] == MODE_INTRA) ? m->dirL[zz] : DC_IDX; }
   if ((y4 & 15) != 0) { const CtuMeta *m = meta_at(e, x4, y4 - 1, &zz); above = (m->pred[zz] == MODE_INTRA) ? m->dirL[zz] : DC_IDX; }
   if (left == above) {
     if (left > 1) { preds[0] = left; preds[1] = ((left + 29) % 32) + 2; preds[2] = ((left - 1) % 32) + 2; }
@@ -783,8 +794,8 @@ HM_DEV inline int ctx_split_flag(const Shared *e, int z, int depth)
   const int r = hm_z2r(z);
   const int x4 = e->ctuX * 16 + (r & 15), y4 = e->ctuY * 16 + (r >> 4);
   int ctx = 0, zz;
-  if (x4 > e->tileX0) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); ctx += m->depth[zz] > depth; }
-  if (y4 > e->tileY0) { const CtuMeta *m = meta_at(e, x4, y4 - 1, &zz); ctx += m->depth[zz] > depth; }
+  if (x4 > e->tileX0 && !in_other_slice(e, x4 - 1, y4)) { const CtuMeta *m = meta_at(e, x4 - 1, y4, &zz); ctx += m->depth[zz] > depth; }
+  if (y4 > e->tileY0 && !in_other_slice(e, x4, y4 - 1)) { const CtuMeta *m = meta_at(e, x4, y4 - 1, &zz); ctx += m->depth[zz] > depth; }
   return ctx;
 }
 
@@ -797,10 +808,10 @@ HM_DEV inline int avail_above_right(const Shared *e, int rtx4, int rty4, int k)
   const int cx = rtx4 & 15, cy = rty4 & 15;
   if (cx + k <= 15) {
     if (cy != 0) return hm_r2z((cy << 4) | cx) > hm_r2z(((cy - 1) << 4) | (cx + k));
-    return rty4 > e->tileY0;
+    return rty4 > e->tileY0 && !in_other_slice(e, rtx4 + k, rty4 - 1);
   }
   if (cy != 0) return 0;
-  return rty4 > e->tileY0 && ((rtx4 >> 4) + 1) * 16 < e->tileX1;
+  return rty4 > e->tileY0 && ((rtx4 >> 4) + 1) * 16 < e->tileX1 && !in_other_slice(e, rtx4 + k, rty4 - 1);
 }
 HM_DEV inline int avail_below_left(const Shared *e, int lbx4, int lby4, int k)
 { // TComDataCU::getPUBelowLeftAdi, TComDataCU.cpp:1244-1300
@@ -808,7 +819,7 @@ HM_DEV inline int avail_below_left(const Shared *e, int lbx4, int lby4, int k)
   const int cx = lbx4 & 15, cy = lby4 & 15;
   if (cy + k <= 15) {
     if (cx != 0) return hm_r2z((cy << 4) | cx) > hm_r2z(((cy + k) << 4) | (cx - 1));
-    return lbx4 > e->tileX0;
+    return lbx4 > e->tileX0 && !in_other_slice(e, lbx4 - 1, lby4 + k);
   }
   return 0;
 }
@@ -826,10 +837,10 @@ HM_DEV HM_NOINLINE void init_adi_pattern(Shared *e, int comp, int px, int py, in
   int cnt = 0;
   HM_PAR_FOR(u, total) {
     int a;
-    if (u == L) a = (x4 > e->tileX0 && y4 > e->tileY0);
-    else if (u > L && u <= L + units) a = (y4 > e->tileY0);
+    if (u == L) a = (x4 > e->tileX0 && y4 > e->tileY0 && !in_other_slice(e, x4 - 1, y4 - 1));
+    else if (u > L && u <= L + units) a = (y4 > e->tileY0 && !in_other_slice(e, x4, y4 - 1));
     else if (u > L + units) a = avail_above_right(e, x4 + units - 1, y4, u - L - units);
-    else if (u >= L - units) a = (x4 > e->tileX0);
+    else if (u >= L - units) a = (x4 > e->tileX0 && !in_other_slice(e, x4 - 1, y4));
     else a = avail_below_left(e, x4, y4 + units - 1, L - units - u);
     flags[u] = (uint8_t)a; cnt += a;
   }
@@ -3010,7 +3021,15 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
   int codedPrev = e->ctuAddr - 1, scanPrev = e->ctuAddr - 1;
   if (P->tile) { const TileCtu t = P->tile[e->ctuAddr]; e->tileX0 = (uint16_t)(t.x0 * 16); e->tileX1 = (uint16_t)(t.x1 * 16); e->tileY0 = (uint16_t)(t.y0 * 16); codedPrev = t.prev; scanPrev = t.scanPrev; }
   else { e->tileX0 = 0; e->tileX1 = (uint16_t)(P->wCtu * 16); e->tileY0 = 0; }
-  e->tilePad = 0;
+  // hm355_set_slices: the slice's first CTU starts the CABAC chain anew, and the neighbouring CTUs before it belong to another slice
+  int lastOfSlice = e->ctuAddr == P->wCtu * P->hCtu - 1;
+  e->otherSlice = 0;
+  if (P->slice) {
+    const SliceCtu s = P->slice[e->ctuAddr]; const int a = e->ctuAddr, w = P->wCtu;
+    if (a == s.first) codedPrev = -1;
+    lastOfSlice = a == s.end - 1;
+    e->otherSlice = (uint16_t)((a - 1 < s.first ? 1 : 0) | (a - w < s.first ? 2 : 0) | (a - w - 1 < s.first ? 4 : 0) | (a - w + 1 < s.first ? 8 : 0));
+  }
   e->cc = e->fb.coef + (size_t)e->ctuAddr * HM_COEF_CTU;
   e->im = e->fb.imeta ? e->fb.imeta + e->ctuAddr : (InterMeta *)0;
   HM_SYNC();
@@ -3093,7 +3112,7 @@ HM_DEV inline void process_ctu(Shared *e, const Params *P, const WorkItem *it, i
   cabac_copy(&e->cur, cb0);
   reset_bits(&e->cur);
   if (e->fb.dqp) { if (hm_lane() == 0) e->ws->dq.flag = 1; HM_SYNC(); }      // TEncCu::encodeCtu :358-361
-  encode_ctu(e, &e->cur, a == numCtus - 1);
+  encode_ctu(e, &e->cur, lastOfSlice);
   cabac_copy(e->fb.endState + a, &e->cur);
   if (e->fb.dqp) {
     const int firstZ = first_coded_cu(e), q = HM_UNI(e->ws->dq.ctuQp), refQp = HM_UNI(e->ws->dq.refQp), flag = HM_UNI(e->ws->dq.flag);

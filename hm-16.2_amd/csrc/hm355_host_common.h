@@ -160,6 +160,55 @@ static inline int hm355_tile_carries(const hm355_tile_tables &t, int tile, int w
   return x0 * 64 + 63 >= width || y0 * 64 + 63 >= height;
 }
 
+// ---- slices (hm355_set_slices) ----
+// SliceMode=1 (FIXED_NUMBER_OF_CTU), TEncSlice::calculateBoundingCtuTsAddrForSlice (TEncSlice.cpp:1097-1182) without tiles: a slice ends
+// ctusPerSlice CTUs after its start or with the picture; under WaveFrontSynchro a slice that starts inside a CTU row ends with that row at the
+// latest.  Returns the number of slices (0: bad arguments) and writes the first `cap` first CTUs.
+static inline int hm355_slice_fixed_ctus(int wCtu, int hCtu, int wpp, int ctusPerSlice, int *firstCtu, int cap)
+{
+  if (wCtu < 1 || hCtu < 1 || ctusPerSlice < 1) return 0;
+  const int n = wCtu * hCtu;
+  int count = 0;
+  for (int a = 0; a < n; count++) {
+    if (firstCtu && count < cap) firstCtu[count] = a;
+    int end = a + ctusPerSlice < n ? a + ctusPerSlice : n;
+    if (wpp && a % wCtu != 0 && a - a % wCtu + wCtu < end) end = a - a % wCtu + wCtu;
+    a = end;
+  }
+  return count;
+}
+struct hm355_slice_tables {
+  std::vector<int> first;                 // [slice] raster address of its first CTU, ascending from 0
+  std::vector<int> start;                 // `first`, then the number of CTUs (Params::sliceStart)
+  std::vector<SliceCtu> ctu;              // [raster address] what the device reads (Params::slice)
+  int count() const { return first.empty() ? 1 : (int)first.size(); }
+};
+// The tables of a partition into `num` slices over wCtu x hCtu CTUs.  Returns NULL, or the reason the partition is refused (then `t` is untouched).
+static inline const char *hm355_build_slices(int wCtu, int hCtu, int wpp, int num, const int *firstCtu, hm355_slice_tables *t)
+{
+  const int n = wCtu * hCtu;
+  if (num < 1 || !firstCtu) return "the partition needs one slice or more, with the first CTU of each";
+  if (firstCtu[0] != 0) return "the first slice does not start at CTU 0";
+  for (int k = 1; k < num; k++) if (firstCtu[k] <= firstCtu[k - 1]) return "the first CTUs are not ascending";
+  if (firstCtu[num - 1] >= n) return "a slice starts past the picture";
+  for (int k = 0; wpp && k < num; k++) {
+    const int a = firstCtu[k], end = k + 1 < num ? firstCtu[k + 1] : n;
+    if (a % wCtu != 0 && end > a - a % wCtu + wCtu) return "under WaveFrontSynchro a slice that starts inside a CTU row must end with that row";
+  }
+  hm355_slice_tables o;
+  o.first.assign(firstCtu, firstCtu + num); o.start = o.first; o.start.push_back(n); o.ctu.resize(n);
+  for (int k = 0; k < num; k++) for (int a = o.start[k]; a < o.start[k + 1]; a++) { o.ctu[a].first = o.start[k]; o.ctu[a].end = o.start[k + 1]; }
+  *t = o;
+  return NULL;
+}
+// the first CTU of slice k starts from the m_integerMv2Nx2N of the CTU before it (process_ctu): its 64x64 CU crosses the picture's right or bottom edge
+static inline int hm355_slice_carries(const hm355_slice_tables &t, int k, int wCtu, int width, int height)
+{
+  if (k == 0) return 0;
+  const int a = t.first[k];
+  return (a % wCtu) * 64 + 63 >= width || (a / wCtu) * 64 + 63 >= height;
+}
+
 // Dependency-ordered launch schedule.  Step s holds every CTU whose inputs (left, above-left, above,
 // above-right CTU and the CABAC hand-off) were produced in steps < s:
 //   WaveFrontSynchro=1 : CTU (x,y) runs at step x + 2y   (2-CTU lag wavefront, TEncSlice.cpp:740-755)
@@ -178,9 +227,11 @@ static inline int hm355_schedule_step(int wCtu, int hCtu, int wpp, int carryLast
 // CTU of the tile before it (hm355_tile_carries; width, height: the picture's) is ordered behind that tile, as carryLastRow does for a WPP row.
 static inline void hm355_build_schedule(int wCtu, int hCtu, int wpp, int nFrames, std::vector<WorkItem> &items, std::vector<int> &stepStart, int carryLastRow = 0,
                                         int firstFrame = 0, int firstCtu = 0, int lastCtu = -1, const hm355_tile_tables *tiles = NULL, int carryTiles = 0,
-                                        int width = 0, int height = 0)
+                                        int width = 0, int height = 0, const hm355_slice_tables *slices = NULL)
 { // CTUs [firstCtu, lastCtu] (raster addresses, i.e. coding order) of the pictures in slots [firstFrame, firstFrame + nFrames): a band of CTUs (the
   // CTUs before it are complete) -- whole CTU rows (hm355_run_rows), or any range (hm355_run_ctus)
+  // slices (hm355_set_slices, without WaveFrontSynchro and without tiles): every slice is a chain of its own, exactly as every tile is; carryTiles
+  // then orders a slice whose first CTU the picture edge cuts (hm355_slice_carries) behind the slice before it
   items.clear(); stepStart.clear();
   if (lastCtu < 0) lastCtu = wCtu * hCtu - 1;
   int steps = hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, wCtu - 1, hCtu - 1) + 1;
@@ -194,11 +245,23 @@ static inline void hm355_build_schedule(int wCtu, int hCtu, int wpp, int nFrames
       if (tileStep[t] + size > steps) steps = tileStep[t] + size;
     }
   }
+  const bool sliced = !tiled && !wpp && slices && slices->count() > 1;
+  std::vector<int> sliceStep, sliceOf;       // step of every slice's first CTU; slice of every CTU
+  if (sliced) {
+    sliceStep.assign(slices->count(), 0); sliceOf.resize(wCtu * hCtu); steps = 0;
+    for (int k = 0; k < slices->count(); k++) {
+      const int size = slices->start[k + 1] - slices->start[k];
+      if (carryTiles && hm355_slice_carries(*slices, k, wCtu, width, height)) sliceStep[k] = sliceStep[k - 1] + slices->start[k] - slices->start[k - 1];
+      if (sliceStep[k] + size > steps) steps = sliceStep[k] + size;
+      for (int a = slices->start[k]; a < slices->start[k + 1]; a++) sliceOf[a] = k;
+    }
+  }
   std::vector<std::vector<WorkItem> > bucket(steps);
   for (int a = firstCtu; a <= lastCtu; a++) {
     const int x = a % wCtu, y = a / wCtu; WorkItem w = {0, x, y, 0};
     int s = hm355_schedule_step(wCtu, hCtu, wpp, carryLastRow, x, y);
     if (tiled) { const int t = tiles->tileOf[a]; s = tileStep[t] + tiles->rsToTs[a] - tiles->rsToTs[tiles->firstCtu[t]]; }
+    if (sliced) s = sliceStep[sliceOf[a]] + a - slices->start[sliceOf[a]];
     bucket[s].push_back(w);
   }
   for (int s = 0; s < steps; s++) {
@@ -212,7 +275,7 @@ static inline void hm355_build_schedule(int wCtu, int hCtu, int wpp, int nFrames
 // needs HM_CTU_WAVES (hm355_core.h), HM_TEAM and HM_TEAM_I (hm355_team.h): both users include hm355_core.h first
 #define HM_WS_MAX 3072   /* 12 searches per CU x 256 CUs is the most that can be resident */
 // the widest step of the dependency schedule: as many CTUs of `frames` pictures as can ever be ready at once
-// chains: independent CABAC chains per picture without WaveFrontSynchro (the tiles of hm355_set_tiles)
+// chains: independent CABAC chains per picture without WaveFrontSynchro (the tiles of hm355_set_tiles, the slices of hm355_set_slices)
 static inline int hm355_max_items_per_step(int wCtu, int hCtu, int wpp, int frames, int chains = 1)
 {
   if (!wpp) return frames * chains;
@@ -242,7 +305,7 @@ struct hm355_launch_plan {
 // hm355_set_lane_share; teamCap: teams the lane's reconstruction windows exist for (the caller grows them to `want` and plans again).
 static inline hm355_launch_plan hm355_plan_launch(int wCtu, int hCtu, int wpp, int maxBatch, int n, int ctu0, int ctu1, int anyInter, int fast,
                                                   int envTeam, int envTeamWaves, int laneShare, long long teamCap, int chains = 1)
-{ // chains: tiles per picture (1: untiled) -- each is a serial chain of CTUs of its own, so n pictures offer n x chains CTUs at a time
+{ // chains: tiles or slices per picture (1: neither) -- each is a serial chain of CTUs of its own, so n pictures offer n x chains CTUs at a time
   hm355_launch_plan p; memset(&p, 0, sizeof(p));
   p.wsCount = hm355_ws_count(wCtu * hCtu, maxBatch);
   p.total = n * (ctu1 - ctu0 + 1);

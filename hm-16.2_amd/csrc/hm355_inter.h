@@ -196,6 +196,7 @@ HM_DEV inline int nb_at(const Shared *e, int x4, int y4, int dir, int curZ, int 
   }
   const int gx = e->ctuX * 16 + nx, gy = e->ctuY * 16 + ny;
   if (gx < e->tileX0 || gy < e->tileY0 || gx >= e->tileX1) return -1;      // outside the tile (the picture, when it has no tiles): bEnforceTileRestriction
+  if (in_other_slice(e, gx, gy)) return -1;                                 // in a CTU of another slice: bEnforceSliceRestriction
   if (gx * 4 >= e->width || gy * 4 >= e->height) return -1;
   const int cx = gx >> 4, cy = gy >> 4;
   if (cy > e->ctuY) return -1;

@@ -6,7 +6,7 @@
 //                            (decideBlkParams :780): the CABAC estimator state chains from CTU to CTU, so one lane walks the picture
 //                            while the wavefront stages its inputs and outputs through LDS; pictures of a batch run side by side
 //   hm355_sao_apply_kernel   offsets applied per sample (TComSampleAdaptiveOffset::offsetBlock, TComSampleAdaptiveOffset.cpp:311)
-// One slice; tiles with LFCrossTileBoundaryFlag = 1 (the merge candidates stay inside the tile, statistics and offsets cross tile edges); SAOLcuBoundary = 0, offset bit shifts 0 (every cfg of the reference).
+// Slices with LFCrossSliceBoundaryFlag = 1 and tiles with LFCrossTileBoundaryFlag = 1 (the merge candidates stay inside the tile, statistics and offsets cross tile edges); SAOLcuBoundary = 0, offset bit shifts 0 (every cfg of the reference).
 #pragma once
 
 enum { SAO_OFF = 0, SAO_NEW = 1, SAO_MERGE = 2, SAO_EO_0 = 0, SAO_EO_90, SAO_EO_135, SAO_EO_45, SAO_BO, SAO_NUM_TYPES };
@@ -197,6 +197,7 @@ extern "C" __global__ void __launch_bounds__(64) hm355_sao_decide_kernel(const P
   for (int a = 0; a < numCtus; a++) {                                                        // decideBlkParams :780-860
     int hasL = (a % wCtu) > 0, hasA = (a / wCtu) > 0;
     if (P->tile) { hasL = (a % wCtu) > P->tile[a].x0; hasA = (a / wCtu) > P->tile[a].y0; }   // TComPic::getSAOMergeAvailability: the candidate lies in the same tile
+    if (P->slice) { const int s0 = P->slice[a].first; hasL = hasL && a - 1 >= s0; hasA = hasA && a - wCtu >= s0; }   // ... and in the same slice
     if (!allDisabled) {
       const int32_t *gc = (const int32_t *)(sp->cand + (size_t)a * 3 * SAO_NUM_TYPES);
       for (int i = lane; i < nC; i += 64) ((int32_t *)sCand)[i] = gc[i];

@@ -336,7 +336,7 @@ HM_DEV inline void team_adopt(Shared *e, const Shared *src, int wave, Pel *win)
   e->width = src->width; e->height = src->height; e->bitDepth = src->bitDepth; e->wCtu = src->wCtu;
   for (int c = 0; c < 3; c++) e->stride[c] = src->stride[c];
   e->ctuX = src->ctuX; e->ctuY = src->ctuY; e->ctuAddr = src->ctuAddr;
-  e->tileX0 = src->tileX0; e->tileX1 = src->tileX1; e->tileY0 = src->tileY0; e->tilePad = 0;
+  e->tileX0 = src->tileX0; e->tileX1 = src->tileX1; e->tileY0 = src->tileY0; e->otherSlice = src->otherSlice;
   e->ws = team_wave_ws(wave); e->cc = e->ws->teamCoef; e->im = (InterMeta *)0; e->mpmZ = -1; e->s8Reuse = 0;
   if (e->fb.dqp && hm_lane() == 0) e->ws->dq = src->ws->dq;    // QP of the CTU, its predictor (m_bEncodeDQP is clear whenever a team searches)
   if (win) {

@@ -186,6 +186,9 @@ struct TileCtu {
   int32_t scanPrev;                  // ... of the CTU before it in tile scan, whatever its tile (m_integerMv2Nx2N carries on), -1 at the picture's first CTU
 };
 struct TileInfo { int32_t firstCtu, scanStart; };   // raster address of the tile's first CTU; CTUs coded before the tile (its place in tile scan)
+// Slices (hm355_set_slices): the slice of a CTU covers raster addresses [first, end).  A neighbouring CTU below `first` belongs to another slice
+// (TComDataCU::CUIsFromSameSliceAndTile, TComDataCU.cpp:310-317) and is unavailable to everything spatial, like a CTU of another tile
+struct SliceCtu { int32_t first, end; };
 
 struct Params {
   int32_t width, height, bitDepth, wpp;
@@ -204,7 +207,9 @@ struct Params {
   int32_t searchRange, bipredRange;  // SearchRange 1..256 (0: 64), BipredSearchRange 1..16 (0: 4)
   const TileCtu *tile;               // hm355_set_tiles: [numCtus] the tile of every CTU (NULL: one tile, the picture)
   const TileInfo *tileInfo;          // [numTiles] the tiles in tile-scan order: one substream each (bitstream pass)
-  int32_t numTiles, tilePad;
+  int32_t numTiles, numSlices;
+  const SliceCtu *slice;             // hm355_set_slices: [numCtus] the slice of every CTU (NULL: one slice, the picture; never with tiles)
+  const int32_t *sliceStart;         // [numSlices + 1] first CTU of every slice, then numCtus: one substream each (bitstream pass)
 };
 
 struct WorkItem { int32_t frame, ctuX, ctuY, pad; };

@@ -93,6 +93,16 @@ class BitsDesc(C.Structure):
                 ("next_cabac_init_type", C.c_int32), ("num_bins", C.c_uint32)]
 
 
+def fixed_ctu_slices(lib, w_ctu, h_ctu, wpp, ctus_per_slice):
+    """hm355_fixed_ctu_slices -> the first CTU of every slice of SliceMode=1 with SliceArgument=ctus_per_slice"""
+    n = lib.hm355_fixed_ctu_slices(w_ctu, h_ctu, int(wpp), int(ctus_per_slice), None, 0)
+    if n < 1:
+        raise ValueError("hm355_fixed_ctu_slices: bad arguments")
+    first = np.zeros(n, np.int32)
+    lib.hm355_fixed_ctu_slices(w_ctu, h_ctu, int(wpp), int(ctus_per_slice), first.ctypes.data, n)
+    return first
+
+
 class PicStatDesc(C.Structure):
     """hm355_picstat_desc: SSD / PSNR / MSE per component and the decoded picture hash of one picture"""
     _fields_ = [("hash_method", C.c_int32), ("pad_right", C.c_int32), ("pad_bottom", C.c_int32), ("ssd", C.c_uint64 * 3),
@@ -117,7 +127,7 @@ EXPORTS = ["hm355_build_id", "hm355_picture_stats_run", "hm355_picture_stats", "
            "hm355_compress_slice_inter", "hm355_compress_slices_inter", "hm355_deblock", "hm355_deblock_run", "hm355_ref_from_slot", "hm355_ref_release", "hm355_ref_bytes", "hm355_ref_export", "hm355_ref_import", "hm355_sao_run",
            "hm355_num_substreams", "hm355_encode_slices_run", "hm355_encode_slice",
            "hm355_upload_file_frames", "hm355_download_file_frames", "hm355_download_org",
-           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_set_motion_search", "hm355_set_tiles", "hm355_uniform_tiles", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_last_launch_shape", "hm355_dist_batch",
+           "hm355_upload", "hm355_run", "hm355_run_begin", "hm355_run_wait", "hm355_set_lane_share", "hm355_set_fast_decisions", "hm355_set_motion_search", "hm355_set_tiles", "hm355_uniform_tiles", "hm355_set_slices", "hm355_fixed_ctu_slices", "hm355_num_slices", "hm355_slice_bits_info", "hm355_run_rows", "hm355_boundary_bytes", "hm355_export_boundary", "hm355_import_boundary", "hm355_download", "hm355_last_run_info", "hm355_last_launch_shape", "hm355_dist_batch",
            "hm355_transform_batch"]
 
 
@@ -147,6 +157,10 @@ def load_library(path=LIB_PATH):
     lib.hm355_set_tiles.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     lib.hm355_uniform_tiles.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.hm355_uniform_tiles.restype = None
+    lib.hm355_set_slices.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.hm355_fixed_ctu_slices.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.hm355_num_slices.argtypes = [C.c_void_p]
+    lib.hm355_slice_bits_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     lib.hm355_set_dqp.argtypes = [C.c_void_p, C.c_int, C.POINTER(DqpDesc)]
     lib.hm355_get_dqp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32)]
     lib.hm355_preanalyze.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -444,6 +458,24 @@ class Encoder:
         cols = np.ascontiguousarray(col_width_ctus if col_width_ctus is not None else [(self.w + 63) // 64], np.int32)
         rows = np.ascontiguousarray(row_height_ctus if row_height_ctus is not None else [(self.h + 63) // 64], np.int32)
         self._check(self.lib.hm355_set_tiles(self.h_, len(cols), cols.ctypes.data, len(rows), rows.ctypes.data, int(lf_cross_tile)), "hm355_set_tiles")
+
+    def set_slices(self, first_ctu=None, lf_cross_slice=1, ctus_per_slice=None):
+        """slices for every later search, SAO and bitstream pass of this encoder (hm355_set_slices): the raster address of the first CTU of every
+        slice, ascending from 0 -- or ctus_per_slice, SliceMode=1's argument (hm355_fixed_ctu_slices); sticky until set again.  No arguments (or
+        [0]): one slice."""
+        if ctus_per_slice is not None:
+            first_ctu = fixed_ctu_slices(self.lib, (self.w + 63) // 64, (self.h + 63) // 64, self.wpp, ctus_per_slice)
+        first = np.ascontiguousarray(first_ctu if first_ctu is not None else [0], np.int32)
+        self._check(self.lib.hm355_set_slices(self.h_, len(first), first.ctypes.data, int(lf_cross_slice)), "hm355_set_slices")
+
+    def slice_bits_info(self, slot=0):
+        """hm355_slice_bits_info -> [(substreams, next cabac_init_type, bins) of every slice of the slot's last bitstream pass]"""
+        n = self.lib.hm355_num_slices(self.h_)
+        out = np.zeros((n, 3), np.uint32)
+        got = self.lib.hm355_slice_bits_info(self.h_, slot, out.ctypes.data, n)
+        if got != n:
+            raise RuntimeError("hm355_slice_bits_info: no bitstream pass since the partition was set")
+        return [(int(a), int(b), int(c)) for a, b, c in out]
 
     def run_wait(self, lane):
         """wait for the launch of `lane`; returns its kernel time in ms (hm355_run_wait)"""

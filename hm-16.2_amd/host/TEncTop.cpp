@@ -58,6 +58,19 @@ Void TEncTop::create()
       exit(EXIT_FAILURE);
     }
   }
+  // slices (--SliceMode=1): a new slice every SliceArgument CTUs, TEncSlice.cpp:1097-1182
+  if (m_sliceMode != 0) {
+    if (m_sliceMode != 1) { fprintf(stderr, "TEncTop::create: SliceMode %d is not supported (1: a fixed number of CTUs per slice)\n", m_sliceMode); hm355_destroy(m_ctx); exit(EXIT_FAILURE); }
+    const Int wCtu = (m_iSourceWidth + 63) / 64, hCtu = (m_iSourceHeight + 63) / 64, wpp = getWaveFrontsynchro() ? 1 : 0;
+    const Int n = hm355_fixed_ctu_slices(wCtu, hCtu, wpp, m_sliceArgument, NULL, 0);
+    std::vector<Int> first(n > 0 ? n : 1, 0);
+    hm355_fixed_ctu_slices(wCtu, hCtu, wpp, m_sliceArgument, first.data(), n);
+    if (n < 1 || hm355_set_slices(m_ctx, n, first.data(), getLFCrossSliceBoundaryFlag()) != HM355_OK) {
+      fprintf(stderr, "TEncTop::create: %s\n", n < 1 ? "bad SliceArgument" : hm355_last_error(m_ctx));
+      hm355_destroy(m_ctx);
+      exit(EXIT_FAILURE);
+    }
+  }
 }
 Void TEncTop::destroy() { for (auto p : m_cListPic) { if (p->getDeviceRef()) hm355_ref_release(m_ctx, p->getDeviceRef()); delete p; } m_cListPic.clear(); if (m_ctx) hm355_destroy(m_ctx); m_ctx = nullptr; }
 Void TEncTop::init() { m_cGOPEncoder.init(this); m_cSliceEncoder.init(this); m_cLoopFilter.init(this); m_cEncSAO.init(this); }
@@ -297,7 +310,7 @@ Void TEncSlice::encodeSlice(TComPic *pcPic, TComOutputBitstream *pcSubstreams, U
   const uint8_t *p = bytes.data();
   for (Int k = 0; k < numSubstreams; p += sizes[k], k++) {
     pcSubstreams[k].getFIFO().assign(p, p + sizes[k]);
-    if (k + 1 < numSubstreams) pcSlice->addSubstreamSize(sizes[k]);      // TEncSlice.cpp:1067-1071 (+ the start code emulation count, a NAL-level matter)
+    if (k + 1 < numSubstreams && hm355_num_slices(ctx) == 1) pcSlice->addSubstreamSize(sizes[k]);      // entry points lie inside a slice; with slices every substream is a slice of its own (TEncSlice.cpp:1067-1071; + the start code emulation count, a NAL-level matter)
   }
   numBinsCoded = bd.num_bins;
   m_pcEncTop->setEncCABACTableIdx(bd.next_cabac_init_type);               // determineCabacInitIdx, TEncSlice.cpp:1083-1093 (cabac_init_present_flag)

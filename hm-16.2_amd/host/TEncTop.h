@@ -141,6 +141,11 @@ public:
   Void setColumnWidth(const std::vector<Int> &w) { m_tileColumnWidth = w; } const std::vector<Int> &getColumnWidth() const { return m_tileColumnWidth; }
   Void setRowHeight(const std::vector<Int> &h) { m_tileRowHeight = h; } const std::vector<Int> &getRowHeight() const { return m_tileRowHeight; }
   Void setLFCrossTileBoundaryFlag(Bool b) { m_bLFCrossTileBoundaryFlag = b; } Bool getLFCrossTileBoundaryFlag() const { return m_bLFCrossTileBoundaryFlag; }
+  // --SliceMode (1: FIXED_NUMBER_OF_CTU, the one mode built), --SliceArgument, --LFCrossSliceBoundaryFlag: TEncTop::create derives the partition as
+  // TEncSlice::calculateBoundingCtuTsAddrForSlice does (hm355_fixed_ctu_slices) and hands it to hm355_set_slices
+  Void setSliceMode(Int i) { m_sliceMode = i; } Int getSliceMode() const { return m_sliceMode; }
+  Void setSliceArgument(Int i) { m_sliceArgument = i; } Int getSliceArgument() const { return m_sliceArgument; }
+  Void setLFCrossSliceBoundaryFlag(Bool b) { m_bLFCrossSliceBoundaryFlag = b; } Bool getLFCrossSliceBoundaryFlag() const { return m_bLFCrossSliceBoundaryFlag; }
   Int getPad(Int i) const { return m_aiPad[i]; }     // TEncCfg::m_aiPad: the driver feeds pictures of the coded size, so both are 0
   Int getSourceWidth() const { return m_iSourceWidth; } Int getSourceHeight() const { return m_iSourceHeight; }
   Int getQP() const { return m_iQP; } Int getGOPSize() const { return m_iGOPSize; } Int getIntraPeriod() const { return m_uiIntraPeriod; }
@@ -152,6 +157,7 @@ protected:
   Int m_decodedPictureHashSEIEnabled = 0, m_aiPad[2] = { 0, 0 };
   Bool m_useEarlySkipDetection = false, m_bUseCbfFastMode = false, m_bUseEarlyCU = false;
   Int m_iFastSearch = 1, m_iSearchRange = 64, m_bipredSearchRange = 4; Bool m_bUseASR = false;
+  Int m_sliceMode = 0, m_sliceArgument = 0; Bool m_bLFCrossSliceBoundaryFlag = true;
   Bool m_tileUniformSpacingFlag = false, m_bLFCrossTileBoundaryFlag = true; Int m_iNumColumnsMinus1 = 0, m_iNumRowsMinus1 = 0; std::vector<Int> m_tileColumnWidth, m_tileRowHeight;
   GOPEntry m_GOPList[16]; Bool m_bUseHADME = true; UInt m_maxNumMergeCand = 5; Int m_TMVPModeId = 1;
 };

@@ -15,6 +15,8 @@
 //   (TEncCfg::setFastSearch, setSearchRange, setBipredSearchRange -> hm355_set_motion_search).  The trailing fast=, me= and hash= arguments come in any order.
 //   ... tiles=<cols>x<rows> as a trailing argument: --TileUniformSpacing=1 --NumTileColumnsMinus1 / --NumTileRowsMinus1; tiles=c:<w0,w1,...>;r:<h0,...>: explicit
 //   spacing, every column width and row height in CTUs (TEncCfg::setNumColumnsMinus1, setColumnWidth, ... -> hm355_set_tiles); one substream per tile
+//   ... slices=<N> as a trailing argument: --SliceMode=1 --SliceArgument=N, a new slice every N CTUs (TEncCfg::setSliceMode, setSliceArgument ->
+//   hm355_fixed_ctu_slices, hm355_set_slices); one substream per slice, in coding order
 // The slice data of every picture (TEncSlice::encodeSlice) goes to <dump.bin>.bits: per picture u32 numSubstreams, then per substream u32 size + bytes.
 #include "TEncTop.h"
 #include <stdio.h>
@@ -82,6 +84,11 @@ int main(int argc, char **argv)
       v[0].pop_back(); v[1].pop_back();          // the configuration names all but the last (TAppEncCfg.cpp:1131-1170)
       enc.setColumnWidth(v[0]); enc.setRowHeight(v[1]);
     } else { fprintf(stderr, "tiles=<cols>x<rows> or tiles=c:<w0,w1,...>;r:<h0,...>\n"); return 2; }
+  }
+  for (int i = 9; i < argc; i++) if (!strncmp(argv[i], "slices=", 7)) {
+    int n = 0; char end;
+    if (sscanf(argv[i] + 7, "%d%c", &n, &end) != 1 || n < 1) { fprintf(stderr, "slices=<CTUs per slice>\n"); return 2; }
+    enc.setSliceMode(1); enc.setSliceArgument(n);
   }
   enc.create(); enc.init();
   FILE *fs = hashMethod ? fopen((std::string(argv[8]) + ".picstat").c_str(), "w") : NULL;

@@ -328,6 +328,34 @@ int hm355_set_motion_search(hm355_ctx *ctx, int fast_search, int search_range, i
 int hm355_set_tiles(hm355_ctx *ctx, int num_cols, const int *col_width_ctus, int num_rows, const int *row_height_ctus, int lf_cross_tile);
 /* uniform tile spacing (uniform_spacing_flag): column c of num_cols is (c + 1) * w_ctu / num_cols - c * w_ctu / num_cols CTUs wide, rows alike */
 void hm355_uniform_tiles(int w_ctu, int h_ctu, int num_cols, int num_rows, int *col_width_ctus, int *row_height_ctus);
+/* Slices (TEncSlice::compressSlice / encodeSlice once per slice, TEncGOP.cpp:1135-1166, :1559): num_slices slices, first_ctu[num_slices] the raster
+ * address of the first CTU of each, ascending from first_ctu[0] == 0.  Sticky and per context like hm355_set_tiles; one slice turns slices off,
+ * which is the state after hm355_create.  Every slice starts with fresh CABAC contexts, and a neighbouring CTU that belongs to another slice is
+ * unavailable to the intra reference samples, the most probable modes, the split and skip flag contexts, the spatial merge / AMVP candidates and
+ * the SAO merge candidates (TComDataCU::CUIsFromSameSliceAndTile); the temporal candidate, the motion search window and -- lf_cross_slice 1,
+ * LFCrossSliceBoundaryFlag -- deblocking and the SAO sample classification cross slice edges.  The results stay in raster order and
+ * hm355_slice_stats stays per picture.  hm355_num_substreams() becomes num_slices and the bitstream pass returns one substream per slice, in coding
+ * order; slice k > 0 of a P / B picture is coded from the context table slice k - 1 chose, only slice 0 from the desc's cabac_init_type; in
+ * hm355_bits_desc next_cabac_init_type is the last slice's and num_bins the sum, hm355_slice_bits_info has the values of every slice.  Every slice
+ * is a chain of CTU searches of its own, so one picture offers num_slices CTUs at a time.
+ * HM355_ERR_ARG with a message in hm355_last_error, the previous partition staying in force: a list that is not ascending from 0 or reaches past
+ * the picture; lf_cross_slice other than 1 (not built); a context with WaveFrontSynchro (not built yet; the reference then ends a slice that
+ * starts inside a CTU row with that row, and a list that breaks this rule is refused for that reason first); tiles in force (and hm355_set_tiles
+ * while slices are in force); cu_qp_delta armed on a slot; a slice open on any slot; a hm355_run_begin launch outstanding.  While slices are on,
+ * hm355_set_dqp (arming), hm355_run_rows, hm355_export_boundary / hm355_import_boundary, hm355_slice_begin(_inter) and hm355_run_ctus are refused
+ * as with tiles.
+ * Out of scope: SliceMode=2 (a byte budget per slice needs the bits of every CTU fed back before the next one starts), SliceMode=3 (whole tiles
+ * per slice), dependent slice segments (SliceSegmentMode), and the level limits on the number of slices, which are the caller's business. */
+int hm355_set_slices(hm355_ctx *ctx, int num_slices, const int *first_ctu, int lf_cross_slice);
+/* SliceMode=1 (--SliceMode=1 --SliceArgument=ctus_per_slice; TEncSlice::calculateBoundingCtuTsAddrForSlice): a new slice every ctus_per_slice
+ * CTUs; with wpp (WaveFrontSynchro) a slice that starts inside a CTU row ends with that row at the latest.  Returns the number of slices (0: bad
+ * arguments) and writes the first CTU of the first `cap` of them. */
+int hm355_fixed_ctu_slices(int w_ctu, int h_ctu, int wpp, int ctus_per_slice, int *first_ctu_out, int cap);
+int hm355_num_slices(const hm355_ctx *ctx);
+/* what the last hm355_encode_slices_run / hm355_encode_slice left for every slice of the picture in `slot`: returns the number of slices and
+ * writes the first `cap` entries (one entry, the picture's, without slices) */
+typedef struct { int32_t num_substreams; int32_t next_cabac_init_type; uint32_t num_bins; } hm355_slice_bits;
+int hm355_slice_bits_info(const hm355_ctx *ctx, int slot, hm355_slice_bits *out, int cap);
 
 /* CTU-row bands (TEncSlice.cpp:740-755,855-858 are the WPP hand-off points a band boundary cuts through): a picture is
  * searched by several devices, each owning a band of whole CTU rows [first_row, last_row] of the pictures in slots
