@@ -45,6 +45,28 @@ static inline bool hostsim_read_yuv(FILE *fi, FrameBuf &fb, const Params &P)
   return true;
 }
 
+// the optional trailing arguments of the replaying twins (hostsim_tiles, hostsim_slices, hostsim_fast), in any order:
+//   fast=<esd><cfm><ecu>             three digits 0 / 1 -> Params::esd / cfm / ecu, as hostsim_fast.cpp takes them from its own arguments
+//   me=<fast>,<range>,<bipred>       -> Params::fullSearch / searchRange / bipredRange, as hostsim_me.cpp takes them from its own arguments
+//   max_inter_slices=<n>             hostsim_me.cpp's cap: the replay ends before P / B slice n + 1 (the one-lane full search is slow)
+// -> true when `a` is one of them (a malformed one ends the program with exit code 2)
+static inline bool hostsim_switch_arg(const char *a, Params &P, int &maxInterSlices)
+{
+  if (!strncmp(a, "fast=", 5)) {
+    if (strlen(a + 5) != 3 || strspn(a + 5, "01") != 3) { fprintf(stderr, "fast=<esd><cfm><ecu>: three digits 0 / 1\n"); exit(2); }
+    P.esd = a[5] - '0'; P.cfm = a[6] - '0'; P.ecu = a[7] - '0';
+    return true;
+  }
+  if (!strncmp(a, "me=", 3)) {
+    int fs, sr, bi; char end;
+    if (sscanf(a + 3, "%d,%d,%d%c", &fs, &sr, &bi, &end) != 3) { fprintf(stderr, "me=<fast>,<range>,<bipred>: three integers\n"); exit(2); }
+    P.fullSearch = fs == 0; P.searchRange = sr; P.bipredRange = bi;
+    return true;
+  }
+  if (!strncmp(a, "max_inter_slices=", 17)) { maxInterSlices = atoi(a + 17); return true; }
+  return false;
+}
+
 // the HMD1 dump (same as the oracle CLI's): header, then per picture the cost / bits / distortion, decisions and coefficients of every CTU and the reconstruction
 static inline void hostsim_write_hmd1_header(FILE *fo, const Params &P, int frames)
 {

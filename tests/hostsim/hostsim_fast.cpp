@@ -1,7 +1,8 @@
 // DEBUGGING AID, NOT PRODUCT: hostsim_inter.cpp's self-checking replay of an HMD2 record stream (every P / B slice re-run with the slice
 // parameters and reference pictures of its record and compared in place) with the fast encoder decisions of hm355_set_fast_decisions --
 // Params::esd / cfm / ecu, the reference's --ESD / --CFM / --ECU -- taken from the command line.  Search only: 'A' and 'B' records are skipped.
-//   hostsim_fast <in.yuv> <dump2.bin> <w> <h> <bitdepth> <wpp> <esd> <cfm> <ecu> [dqp.bin]   exit code 0 = every inter slice bit-exact
+//   hostsim_fast <in.yuv> <dump2.bin> <w> <h> <bitdepth> <wpp> <esd> <cfm> <ecu> [dqp.bin] [me=<fast>,<range>,<bipred>] [max_inter_slices=<n>]
+// exit code 0 = every inter slice replayed is bit-exact; me= and max_inter_slices= (hostsim_common.h: hostsim_switch_arg) come last, in any order
 // dqp.bin (clips encoded with cu_qp_delta): per 'S' record in stream order int32 m_bEncodeDQP on entry, then one int8 QP per CTU.
 #include "hostsim_common.h"
 #include <map>
@@ -22,6 +23,8 @@ int main(int argc, char **argv)
   g_p = data.data(); g_off = 4;
   Params P; hostsim_params(P, w, h, bd, atoi(argv[6]));
   P.esd = atoi(argv[7]); P.cfm = atoi(argv[8]); P.ecu = atoi(argv[9]);
+  int maxSlices = 1 << 30;
+  while (argc > 10 && hostsim_switch_arg(argv[argc - 1], P, maxSlices)) argc--;
   FILE *fq = argc > 10 ? fopen(argv[10], "rb") : NULL;
   if (argc > 10 && !fq) { perror("open"); return 1; }
   const int nctu = P.wCtu * P.hCtu;
@@ -81,6 +84,7 @@ int main(int argc, char **argv)
     int32_t flagIn = 0; std::vector<int8_t> ctuQp(nctu);
     if (fq && (fread(&flagIn, 4, 1, fq) != 1 || fread(ctuQp.data(), 1, nctu, fq) != (size_t)nctu)) { fprintf(stderr, "bad cu_qp_delta inputs\n"); return 4; }
     if (sliceType != HM_P_SLICE && sliceType != HM_B_SLICE) continue;
+    if (nP == maxSlices) break;
     nP++;
     FrameBuf fb; hostsim_alloc_frame(fb, P);
     fseek(fy, (long)(frameBytes * poc), SEEK_SET);

@@ -3,7 +3,8 @@
 // Params::slice as the library puts it -- I pictures too, CTUs in the order of hm355_build_schedule.  Search only: 'A' and 'B' records are skipped.
 // The stream holds one 'S' record per picture: the complete picture, as the reference leaves it after the last slice.
 //   hostsim_slices <in.yuv> <dump2.bin> <w> <h> <bitdepth> <first CTUs, e.g. 0,8,16>       ("0": one slice, Params::slice NULL)
-// exit code 0 = every picture is bit-exact
+//                  [fast=<esd><cfm><ecu>] [me=<fast>,<range>,<bipred>] [max_inter_slices=<n>]   (hostsim_common.h: hostsim_switch_arg; n counts pictures here)
+// exit code 0 = every picture replayed is bit-exact
 #include "hostsim_common.h"
 #include <map>
 
@@ -28,6 +29,8 @@ int main(int argc, char **argv)
   { const char *why = hm355_build_slices(P.wCtu, P.hCtu, 0, (int)first.size(), first.data(), &slices);
     if (why) { fprintf(stderr, "slices: %s\n", why); return 2; }
     if (slices.count() > 1) { P.slice = slices.ctu.data(); P.sliceStart = slices.start.data(); P.numSlices = slices.count(); } }
+  int maxInter = 1 << 30, nInter = 0;
+  for (int i = 7; i < argc; i++) if (!hostsim_switch_arg(argv[i], P, maxInter)) { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   const int nctu = P.wCtu * P.hCtu;
   std::map<int, FinalPic> finals;
   const size_t frameBytes = (size_t)w * h * 3 / 2 * (bd == 8 ? 1 : 2);
@@ -79,6 +82,7 @@ int main(int argc, char **argv)
     std::vector<uint16_t> wantRec[3];
     for (int c = 0; c < 3; c++) { wantRec[c].resize((size_t)(w >> (c ? 1 : 0)) * (h >> (c ? 1 : 0))); rdbuf(wantRec[c].data(), wantRec[c].size() * 2); }
     const bool inter = sliceType == HM_P_SLICE || sliceType == HM_B_SLICE;
+    if (inter && nInter++ == maxInter) break;
     nS++;
     FrameBuf fb; hostsim_alloc_frame(fb, P);
     fseek(fy, (long)(frameBytes * poc), SEEK_SET);

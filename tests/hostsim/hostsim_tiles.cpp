@@ -2,7 +2,8 @@
 // reference pictures of its record and compared in place) with the tile layout of hm355_set_tiles taken from the command line and put into
 // Params::tile as the library puts it -- I slices too, CTUs in the order of hm355_build_schedule.  Search only: 'A' and 'B' records are skipped.
 //   hostsim_tiles <in.yuv> <dump2.bin> <w> <h> <bitdepth> <col widths, e.g. 4,5> <row heights, e.g. 2,1>       ("0" "0": no tiles, Params::tile NULL)
-// exit code 0 = every slice is bit-exact
+//                 [fast=<esd><cfm><ecu>] [me=<fast>,<range>,<bipred>] [max_inter_slices=<n>]                   (hostsim_common.h: hostsim_switch_arg)
+// exit code 0 = every slice replayed is bit-exact
 #include "hostsim_common.h"
 #include <map>
 
@@ -30,6 +31,8 @@ int main(int argc, char **argv)
     if (why) { fprintf(stderr, "tiles: %s\n", why); return 2; }
     if (tiles.count() > 1) P.tile = tiles.ctu.data();
   }
+  int maxInter = 1 << 30, nInter = 0;
+  for (int i = 8; i < argc; i++) if (!hostsim_switch_arg(argv[i], P, maxInter)) { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   const int nctu = P.wCtu * P.hCtu;
   std::map<int, FinalPic> finals;
   const size_t frameBytes = (size_t)w * h * 3 / 2 * (bd == 8 ? 1 : 2);
@@ -81,6 +84,7 @@ int main(int argc, char **argv)
     std::vector<uint16_t> wantRec[3];
     for (int c = 0; c < 3; c++) { wantRec[c].resize((size_t)(w >> (c ? 1 : 0)) * (h >> (c ? 1 : 0))); rdbuf(wantRec[c].data(), wantRec[c].size() * 2); }
     const bool inter = sliceType == HM_P_SLICE || sliceType == HM_B_SLICE;
+    if (inter && nInter++ == maxInter) break;
     nS++;
     FrameBuf fb; hostsim_alloc_frame(fb, P);
     fseek(fy, (long)(frameBytes * poc), SEEK_SET);

@@ -33,7 +33,8 @@ def slice_of(first, n):
 
 def load_slices_case(name):
     """-> (cfg, one 'S' record per picture -- the last one the reference wrote, the complete picture --, {poc: 'F'}, {poc: 'A'},
-    {poc: ['B' record of every slice, in coding order]}, the fixture's own arrays (slice_first_ctu, slice_arg, diff_first_ctu_vs_off, qp))"""
+    {poc: ['B' record of every slice, in coding order]}, the fixture's own arrays (slice_first_ctu, slice_arg, diff_first_ctu_vs_off, qp)).
+    Also loads a clip of one slice per picture (the unsliced combo_* clips: one 'B' record per picture, no diff_first_ctu_vs_off)"""
     recs, sao = [], {}
     cfg, slices, finals = common.load_ldp_case(name, records=recs, sao=sao)
     bits = {}
@@ -41,5 +42,5 @@ def load_slices_case(name):
         if r["tag"] == "B":
             bits.setdefault(r["poc"], []).append(r)
     g = np.load(os.path.join(common.GOLD, name + ".npz"))
-    extra = {k: g[k] for k in ("slice_first_ctu", "slice_arg", "diff_first_ctu_vs_off", "qp")}
+    extra = {k: g[k] for k in ("slice_first_ctu", "slice_arg", "diff_first_ctu_vs_off", "qp") if k in g}
     return cfg, slices, finals, sao, bits, extra

@@ -27,17 +27,20 @@ def _want_feedback(r, w, h):
     return want["total_bits"].astype(np.int64), np.where(coded, r["dqp"]["qp"][:, 0].astype(np.int64), -999)
 
 
-def _replay(hm, name, mode, slots=1):
+def _replay(hm, name, mode, slots=1, setup=None):
     """The clip in coding order with the closed loop on slot 0 (search -> deblocking -> SAO -> slice data -> device-resident reference).
     mode "whole": hm355_set_ctu_rc for every CTU, then the whole-slice search (hm355_run / compress_inter); "ctu": one CTU per hm355_run_ctus call
     with hm355_set_ctu_rc before and hm355_ctu_rc_feedback after it; "row": one CTU row per call.  slots > 1: the same picture in every slot, driven
-    by hm355_run_ctus(first_slot=0, n=slots, ...); every slot is compared with the fixture."""
+    by hm355_run_ctus(first_slot=0, n=slots, ...); every slot is compared with the fixture.  setup(enc): called once on the new context before the
+    first picture (the sticky setters of a clip encoded with further options)."""
     saod, bitd = {}, {}
     cfg, slices, finals = common.load_ldp_case(name, sao=saod, bits=bitd)
     w, h, bd = cfg["width"], cfg["height"], cfg["bit_depth"]
     wc = (w + 63) // 64
     rate = np.zeros((3, 8), np.float64)
     enc = hm.Encoder(w, h, bd, cfg["wpp"], max_batch=slots)
+    if setup is not None:
+        setup(enc)
     n = enc.num_ctus
     dev_refs = {}
     for r in slices:

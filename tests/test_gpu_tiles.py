@@ -139,6 +139,78 @@ def test_hip_tiled_batch_of_80_runs_as_160_chains(hm):
     enc.close()
 
 
+def _pipeline(enc, recs, saod, rates):
+    """hm355_deblock_run, hm355_sao_run and hm355_encode_slices_run once over slots 0..len(recs)-1, every slot with the descriptor of its own
+    'S' record and its own SAO disabled-rate table (updated in place) -> per slot (finished picture, SAO flags, SAO parameters, substreams, next
+    context table, bins)"""
+    enc.deblock_run([(int(r["slice_type"]), int(r["qp"]), r["ref_poc"]) for r in recs])
+    sao = enc.sao_run([dict(qp=int(r["qp"]), cabac_init_type=int(r["cabac_init_type"]), depth=saod[int(r["poc"])]["depth"], disabled_rate=rate,
+                            chroma_weight=float(r["weight_cb"]), **{"lambda": float(r["lambda"])}) for r, rate in zip(recs, rates)])
+    bits = enc.encode_slices_run([dict(slice_type=int(r["slice_type"]), qp=int(r["qp"]), cabac_init_type=int(r["cabac_init_type"]), num_ref_idx=r["num_ref_idx"],
+                                       mvd_l1_zero=int(r["mvd_l1_zero"]), max_merge_cand=int(r["max_merge_cand"]), sao_enabled=(en[0], en[1])) for r, (en, _) in zip(recs, sao)])
+    return [(enc.download(s, want_ctus=False)[0], sao[s][0], sao[s][1]) + bits[s] for s in range(len(recs))]
+
+
+def test_hip_tiled_batch_of_different_pictures_through_the_pipeline(hm):
+    """a DIFFERENT picture in every slot of a tiled launch, and of the loop filter and bitstream passes behind it: the two I pictures of the
+    all-intra 2 x 1 clip in slots 0 and 1 of one hm355_run; the three P slices of the low-delay 2 x 2 clip in one hm355_compress_slices_inter
+    call (references: the fixture's finished pictures), which leaves its results resident in slots 0..2.  Then one hm355_deblock_run, one
+    hm355_sao_run and one hm355_encode_slices_run over all slots.  Every slot's CTUs, finished picture, SAO parameters and substreams equal its
+    own 'S' / 'F' / 'A' / 'B' records -- a launch that read another slot's neighbour, hand-off state or tile table entry would not -- and
+    equal the same picture taken through the same calls alone on a context of one slot.
+    The pictures alone come first, the whole clip in coding order: SAO's m_saoDisabledRate runs from picture to picture (POC 2 of the low-delay
+    clip, depth 1, has chroma SAO off because of the I picture's rate), so every slot of the batch is handed the table as it stood before its
+    picture."""
+    for name, pick in ((TILE_CASES[0], lambda r: True), (TILE_CASES[2], lambda r: int(r["slice_type"]) == 1)):
+        saod, bitd = {}, {}
+        cfg, slices, finals = common.load_ldp_case(name, sao=saod, bits=bitd)
+        cols, rows, _ = fixture_layout(name)
+        recs = [r for r in slices if pick(r)]
+        n, inter = len(recs), int(recs[0]["slice_type"]) != 2
+        assert n == (3 if inter else 2) and len(set(int(r["poc"]) for r in recs)) == n
+
+        def search(enc, some):
+            if int(some[0]["slice_type"]) != 2:
+                out = enc.compress_inter_batch([(_frame(cfg, r["poc"]),) + common.ldp_slice_inputs(r, finals) for r in some])
+                return [(o[0], o[1], o[2]) for o in out]
+            for s, r in enumerate(some):
+                enc.upload(s, _frame(cfg, r["poc"]))
+            sl = (hm.SliceDesc * len(some))(*[hm.SliceDesc(2, int(r["qp"]), float(r["lambda"]), float(r["weight_cb"])) for r in some])
+            enc._check(enc.lib.hm355_run(enc.h_, len(some), sl), "hm355_run")
+            return [enc.download(s)[:2] + (None,) for s in range(len(some))]
+
+        alone, rate, rate_before, single = _encoder(hm, cfg, name), np.zeros((3, 8), np.float64), {}, {}
+        for r in slices:
+            rate_before[int(r["poc"])] = rate.copy()
+            one, = search(alone, [r])
+            single[int(r["poc"])] = (one,) + _pipeline(alone, [r], saod, [rate])[0]
+        alone.close()
+        assert not inter or any(rate_before[int(r["poc"])].any() for r in recs), "the rate table should matter to a slot"
+        enc = _encoder(hm, cfg, name, max_batch=n)
+        got = search(enc, recs)
+        shape = enc.last_launch_shape()
+        assert shape["tickets"] == n * enc.num_ctus and shape == _want_shape(enc.num_ctus, len(cols) * len(rows), inter, True, pictures=n, max_batch=n), shape
+        piped = _pipeline(enc, recs, saod, [rate_before[int(r["poc"])].copy() for r in recs])
+        enc.close()
+        for s, r in enumerate(recs):
+            poc, what = int(r["poc"]), f"{name} POC {int(r['poc'])} in slot {s} of {n}"
+            _assert_slice(got[s], r, what)
+            fin, en, params, subs, nxt, bins = piped[s]
+            assert (en[0], en[1]) == tuple(saod[poc]["enabled"]), f"{what}: slice-level SAO flags {en} vs {saod[poc]['enabled']}"
+            assert np.array_equal(common.normalise_sao(params), common.normalise_sao(saod[poc]["sao"])), f"{what}: SAO parameters"
+            for c in range(3):
+                assert np.array_equal(fin[c], finals[poc]["rec"][c]), f"{what}: finished picture plane {c}"
+            assert subs == bitd[poc]["substreams"] and len(subs) == len(cols) * len(rows), f"{what}: slice data bytes"
+            assert (nxt, bins) == (bitd[poc]["next_cabac_init_type"], bitd[poc]["num_bins"]), f"{what}: next context table / bin count"
+            one, afin, aen, aparams, asubs, anxt, abins = single[poc]
+            for k in (1, 2):
+                if one[k] is not None:
+                    for f in one[k].dtype.names:
+                        assert np.array_equal(one[k][f], got[s][k][f]), f"{what}: {f} differs from the picture searched alone"
+            assert all(np.array_equal(one[0][c], got[s][0][c]) and np.array_equal(afin[c], fin[c]) for c in range(3)), f"{what}: planes differ from the picture alone"
+            assert aen == en and np.array_equal(common.normalise_sao(aparams), common.normalise_sao(params)) and (asubs, anxt, abins) == (subs, nxt, bins), f"{what}: SAO / slice data differ from the picture alone"
+
+
 @pytest.mark.parametrize("name,mode,tiles", [(TILE_CASES[2], "ldp", "tiles=2x2"), (TILE_CASES[1], "lf", "tiles=c:4,4,5;r:1,1")])
 def test_cpp_host_mirror_with_tiles(tmp_path, name, mode, tiles):
     """hm355_encmain tiles=...: from the raw YUV through search, loop filters, slice data and device-resident references; every substream of
